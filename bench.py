@@ -21,6 +21,17 @@ server process (which becomes TP rank 0 of the group via the inherited
 torchrun env) and drives the client load; ranks >0 run the broadcast worker
 loop.  The window barrier spans all ranks, so rank 0's elapsed is the MAX
 over ranks by construction.
+
+A plain run sets up, warms up, times the steps and prints the result line.
+``--full`` additionally measures p50 TTFT with probe requests after the
+window.  ``--dump-outputs DIR`` writes ``DIR/output_token_ids.npy`` after the
+timed steps: one row per request with the generated token ids its caller
+received.  Engine mode dumps every token of every request up to the last
+timed step.  Serve mode dumps the first warmup+steps tokens of every stream,
+recovered from the streamed text (where the window falls in a stream's decode
+depends on arrival timing, so a fixed range is used).  Prompts and weights
+are seeded and decoding is greedy, so the same arguments give the same
+inputs and the same token ids every run.
 """
 
 from __future__ import annotations
@@ -59,8 +70,46 @@ def parse_args():
     p.add_argument("--http-port", type=int, default=18080)
     p.add_argument("--timing", action="store_true",
                    help="engine mode: per-phase step timing to stderr")
-    p.add_argument("--server-log", type=str, default="bench_server.log")
+    p.add_argument("--server-log", type=str, default=None,
+                   help="keep the server's output in this file (default: an "
+                        "unnamed temporary file, shown only on failure)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure p50 TTFT (extra probe requests after "
+                        "the timed window); a plain run times the steps only")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write generated token ids as callers receive them to "
+                        "DIR/output_token_ids.npy (float32)")
     return p.parse_args()
+
+
+_FILLER_RE = None
+
+
+def text_to_token_ids(text: str) -> list:
+    """Recover token ids from text decoded by the synthetic byte-level
+    tokenizer: ``<extra_N>`` is vocab id 260+N (4 specials + 256 bytes come
+    first); any other character came from byte tokens and is recorded as
+    its negated code point so it cannot collide with a filler id."""
+    global _FILLER_RE
+    if _FILLER_RE is None:
+        import re
+
+        _FILLER_RE = re.compile(r"<extra_(\d+)>|(.)", re.DOTALL)
+    return [260 + int(m.group(1)) if m.group(1) is not None
+            else -ord(m.group(2)) for m in _FILLER_RE.finditer(text)]
+
+
+def dump_outputs(dirname: str, rows: list, width: int) -> None:
+    """One row per request: its first ``width`` generated token ids
+    (zero-padded), float32 so two builds can be compared with numpy."""
+    import numpy as np
+
+    arr = np.zeros((len(rows), width), dtype=np.float32)
+    for i, row in enumerate(rows):
+        row = row[:width]
+        arr[i, :len(row)] = row
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "output_token_ids.npy"), arr)
 
 
 def result_json(args, *, value, ms_per_step, tp, extra_config):
@@ -130,7 +179,7 @@ def engine_config(args, device: str, tp: int):
     )
 
 
-async def serve_drive(args, gen_budget: int, stabilize_s: float) -> dict:
+async def serve_drive(args, gen_budget: int, stabilize_s: float, srv) -> dict:
     """Client side: C always-on streams, exactly-K-steps window, TTFT probes."""
     import grpc
     import grpc.aio
@@ -155,7 +204,9 @@ async def serve_drive(args, gen_budget: int, stabilize_s: float) -> dict:
             pass
         if time.time() > deadline:
             raise TimeoutError("server never became healthy")
-        await asyncio.sleep(2)
+        if srv.poll() is not None:
+            raise RuntimeError(f"server exited with status {srv.returncode}")
+        await asyncio.sleep(0.25)
 
     channel = grpc.aio.insecure_channel(
         target, options=[("grpc.max_concurrent_streams", 4096)])
@@ -166,6 +217,8 @@ async def serve_drive(args, gen_budget: int, stabilize_s: float) -> dict:
     first_token_evt = [asyncio.Event() for _ in range(args.batch)]
     # per-stream delivery log: (monotonic_ts, delta_tokens)
     deliveries: list[list] = [[] for _ in range(args.batch)]
+    # per-stream received text pieces (kept only for --dump-outputs)
+    texts: list[list] = [[] for _ in range(args.batch)]
     ttfts: list[float] = []
 
     async def one_stream(i: int, max_new: int, probe: bool = False):
@@ -192,6 +245,8 @@ async def serve_drive(args, gen_budget: int, stabilize_s: float) -> dict:
                     if not probe:
                         deliveries[i].append(
                             (now, msg.generated_token_count - seen))
+                        if args.dump_outputs:
+                            texts[i].append(msg.text)
                     seen = msg.generated_token_count
         except grpc.aio.AioRpcError:
             pass  # stream cancelled at teardown
@@ -227,9 +282,10 @@ async def serve_drive(args, gen_budget: int, stabilize_s: float) -> dict:
     window = await asyncio.get_event_loop().run_in_executor(None, _post)
     t0, t1 = window["t0"], window["t1"]
 
-    # p50 TTFT probes while the batch is still decoding (loaded TTFT)
-    for _ in range(args.ttft_samples):
-        await one_stream(0, 2, probe=True)
+    if args.full:
+        # p50 TTFT probes while the batch is still decoding (loaded TTFT)
+        for _ in range(args.ttft_samples):
+            await one_stream(0, 2, probe=True)
 
     # allow in-flight deliveries to land, then stop the load
     await asyncio.sleep(0.5)
@@ -241,6 +297,13 @@ async def serve_drive(args, gen_budget: int, stabilize_s: float) -> dict:
     wire_tokens = sum(
         d for log in deliveries for (ts, d) in log if t0 <= ts < t1)
     ttfts.sort()
+    if args.dump_outputs:
+        # The window's position in each stream's decode depends on arrival
+        # timing, so the dump is a fixed range: every stream has received
+        # at least warmup+steps tokens when the window closes.
+        dump_outputs(args.dump_outputs,
+                     [text_to_token_ids("".join(t)) for t in texts],
+                     args.warmup + args.steps)
     return {
         "window": window,
         "wire_tokens": wire_tokens,
@@ -273,7 +336,18 @@ def run_serve(args, device: str) -> None:
         cmd += ["--num-gpus", str(args.gpus)]
     env = dict(os.environ)
     env["VTA_BENCH"] = "1"
-    log = open(args.server_log, "w")
+    # the server imports the package next to this file whatever the cwd is
+    here = os.path.dirname(os.path.abspath(__file__))
+    env["PYTHONPATH"] = os.pathsep.join(
+        p for p in (here, env.get("PYTHONPATH")) if p)
+    if args.server_log:
+        log = open(args.server_log, "w")
+    else:
+        # no file asked for: nothing is written next to the caller (the
+        # working directory may be read-only); the tail is shown on failure
+        import tempfile
+
+        log = tempfile.TemporaryFile("w+")
     srv = subprocess.Popen(cmd, stdout=log, stderr=log, env=env)
 
     # budget so no stream finishes inside ramp+stabilization+warmup+window,
@@ -286,7 +360,13 @@ def run_serve(args, device: str) -> None:
         raise SystemExit(
             f"context too small for the step window: room={room}")
     try:
-        res = asyncio.run(serve_drive(args, gen_budget, stabilize_s))
+        res = asyncio.run(serve_drive(args, gen_budget, stabilize_s, srv))
+    except BaseException:
+        if not args.server_log:
+            log.seek(0)
+            print("[bench] server output (tail):\n" + log.read()[-4000:],
+                  file=sys.stderr)
+        raise
     finally:
         srv.terminate()
         try:
@@ -428,9 +508,15 @@ def run_engine(args, device: str) -> None:
     tokens_per_s = produced / elapsed
     ms_per_step = elapsed / args.steps * 1e3
 
-    # TTFT: fresh single request, time to first sampled token
+    if args.dump_outputs:
+        # every token each request has generated up to the last timed step
+        rows = [list(engine.scheduler.get_request(f"bench-{i}").output_token_ids)
+                for i in range(args.batch)]
+        dump_outputs(args.dump_outputs, rows, max(len(r) for r in rows))
+
+    # TTFT (--full only): fresh single request, time to first sampled token
     ttfts = []
-    for i in range(args.ttft_samples):
+    for i in range(args.ttft_samples if args.full else 0):
         rid = f"ttft-{i}"
         engine.add_request(
             rid, None, synth_prompt(args.prompt_len),
@@ -445,18 +531,18 @@ def run_engine(args, device: str) -> None:
                 first = time.perf_counter()
         ttfts.append((first - start) * 1e3)
     ttfts.sort()
-    p50_ttft_ms = ttfts[len(ttfts) // 2]
+    p50_ttft_ms = round(ttfts[len(ttfts) // 2], 2) if ttfts else None
 
     for i in range(args.batch):
         engine.abort_request(f"bench-{i}")
-    for i in range(args.ttft_samples):
+    for i in range(len(ttfts)):
         engine.abort_request(f"ttft-{i}")
     if tp > 1:
         tp_broadcast_object(("stop",))
 
     out = result_json(
         args, value=tokens_per_s, ms_per_step=ms_per_step, tp=tp,
-        extra_config={"p50_ttft_ms": round(p50_ttft_ms, 2)},
+        extra_config={"p50_ttft_ms": p50_ttft_ms},
     )
     print(json.dumps(out))
 

@@ -4,6 +4,7 @@
 from __future__ import annotations
 
 import asyncio
+import os
 import socket
 import threading
 import time
@@ -69,7 +70,14 @@ def make_tiny_lora(path: str, *, hidden=64, q_out=64, kv_out=32, layers=2, r=4, 
 def _servers():
     from vllm_tgis_adapter_amd.__main__ import parse_args, start_servers
 
-    make_tiny_lora("tests/fixtures/adapters/tiny-lora")
+    # anchored at this file so the suite does not depend on the caller's cwd
+    adapters = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                            "fixtures", "adapters")
+    # the adapter is committed; regenerate only if absent, so the suite also
+    # runs from a read-only checkout
+    if not os.path.exists(
+            os.path.join(adapters, "tiny-lora", "adapter_model.safetensors")):
+        make_tiny_lora(os.path.join(adapters, "tiny-lora"))
 
     grpc_port, http_port = get_free_port(), get_free_port()
     argv = [
@@ -80,7 +88,7 @@ def _servers():
         "--port", str(http_port),
         "--max-num-batched-tokens", "512",
         "--max-num-seqs", "32",
-        "--adapter-cache", "tests/fixtures/adapters",
+        "--adapter-cache", adapters,
     ]
     args = parse_args(argv)
 

@@ -13,12 +13,13 @@ from pathlib import Path
 REPO = Path(__file__).resolve().parent.parent
 
 
-def test_bench_serve_cpu_dry_run():
+def test_bench_serve_cpu_dry_run(tmp_path):
     proc = subprocess.run(
         [sys.executable, str(REPO / "bench.py"),
          "--steps", "8", "--warmup", "2", "--batch", "16",
          "--grpc-port", "18913", "--http-port", "18914",
-         "--server-log", "/tmp/test_bench_serve_server.log"],
+         "--server-log", str(tmp_path / "server.log"),
+         "--full", "--dump-outputs", str(tmp_path / "out")],
         capture_output=True, text=True, timeout=300, cwd=str(REPO),
     )
     assert proc.returncode == 0, proc.stderr[-2000:]
@@ -31,9 +32,17 @@ def test_bench_serve_cpu_dry_run():
     assert out["config"]["p50_ttft_ms"] > 0
     assert out["config"]["engine_tokens_per_s"] > 0
     assert out["data"] == "synthetic"
+    # --dump-outputs: one row per stream, warmup+steps generated token ids
+    import numpy as np
+
+    ids = np.load(tmp_path / "out" / "output_token_ids.npy")
+    assert ids.dtype == np.float32 and ids.shape == (16, 10)
+    assert (ids != 0).any(axis=1).all()
+    # every stream sends the same prompt under greedy decoding (fp32 on CPU)
+    assert (ids == ids[0]).all()
 
 
-def test_bench_serve_tp2_torchrun_cpu():
+def test_bench_serve_tp2_torchrun_cpu(tmp_path):
     """World-2 dry run of the DRIVER's exact invocation shape.
 
     The round-end scale bench launches ``torch.distributed.run --nnodes=1
@@ -49,7 +58,7 @@ def test_bench_serve_tp2_torchrun_cpu():
          "--master-port", "29731", str(REPO / "bench.py"),
          "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch", "8",
          "--grpc-port", "18915", "--http-port", "18916",
-         "--server-log", "/tmp/test_bench_serve_tp2_server.log"],
+         "--server-log", str(tmp_path / "server.log")],
         capture_output=True, text=True, timeout=420, cwd=str(REPO),
     )
     assert proc.returncode == 0, (proc.stdout[-1500:], proc.stderr[-2500:])
@@ -83,13 +92,13 @@ def test_bench_engine_tp2_torchrun_cpu():
     assert out["value"] > 0
 
 
-def test_bench_serve_top_n_dry_run():
+def test_bench_serve_top_n_dry_run(tmp_path):
     """--top-n drives the wire logprob/token-detail path end to end."""
     proc = subprocess.run(
         [sys.executable, str(REPO / "bench.py"),
          "--steps", "6", "--warmup", "2", "--batch", "8", "--top-n", "5",
          "--grpc-port", "18919", "--http-port", "18920",
-         "--server-log", "/tmp/test_bench_serve_topn_server.log"],
+         "--server-log", str(tmp_path / "server.log")],
         capture_output=True, text=True, timeout=300, cwd=str(REPO),
     )
     assert proc.returncode == 0, proc.stderr[-2000:]

@@ -370,7 +370,12 @@ def test_lora_unique_ids_start_at_1000001():
         AdapterStore, validate_adapters,
     )
 
-    store = AdapterStore(cache_path="tests/fixtures/adapters", adapters={})
+    import os
+
+    store = AdapterStore(
+        cache_path=os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                                "fixtures", "adapters"),
+        adapters={})
     assert store.next_unique_id == 1000001
 
     from vllm_tgis_adapter_amd.engine.types import LoRARequest

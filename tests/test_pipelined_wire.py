@@ -25,13 +25,13 @@ REPO = Path(__file__).resolve().parent.parent
 
 
 @pytest.fixture(scope="module")
-def pipelined_server():
+def pipelined_server(tmp_path_factory):
     from tests.conftest import get_free_port
 
     gport, hport = get_free_port(), get_free_port()
     env = dict(os.environ)
     env.update({"VTA_PIPELINE": "1", "VTA_PIPELINE_MIN": "1"})
-    log = open("/tmp/test_pipelined_wire_server.log", "w")
+    log = open(tmp_path_factory.mktemp("pipelined_wire") / "server.log", "w")
     proc = subprocess.Popen(
         [sys.executable, "-m", "vllm_tgis_adapter_amd",
          "--model", "tiny-llama", "--dtype", "float32",

@@ -7,6 +7,9 @@ the CPU-CI case) and that the ctypes binding path activates when
 
 import subprocess
 import sys
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parent.parent
 
 
 def test_disabled_by_default_noop():
@@ -38,7 +41,7 @@ def test_enabled_via_env_subprocess():
         [sys.executable, "-c", code],
         env={"VTA_ROCTX": "1", "PATH": "/usr/bin:/bin",
              "LD_LIBRARY_PATH": "/opt/rocm/lib"},
-        capture_output=True, text=True, timeout=120, cwd="/root/repo",
+        capture_output=True, text=True, timeout=120, cwd=str(REPO),
     )
     assert out.returncode == 0, out.stderr
     assert "ROCTX_OK" in out.stdout

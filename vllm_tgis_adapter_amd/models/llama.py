@@ -71,6 +71,10 @@ class Attention(nn.Module):
     ) -> torch.Tensor:
         qkv = self.qkv_proj(hidden, lora=self._qkv_lora)
         q, k, v = qkv.split([self.q_local, self.kv_local, self.kv_local], dim=-1)
+        # the HIP kernels below address rows densely ([T, heads*head_dim]); on
+        # the strided split views the in-place rotary made token blocks
+        # overwrite each other's rows, a race that changed results run to run
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         q, k = ops.rotary_embedding(positions, q, k, self.head_dim, cos_sin_cache)
         t = hidden.shape[0]
         q = q.view(t, self.num_heads, self.head_dim)
