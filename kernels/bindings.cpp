@@ -89,6 +89,11 @@ void launch_lora_expand(T*, const float*, const T*, const int*, const float*,
 template <typename T>
 void launch_sample_argmax(long*, const T*, const float*, const float*, int,
                           int, hipStream_t);
+template <typename T>
+void launch_sample_topk_topp(long*, int*, const T*, const float*,
+                             const float*, const int*, const float*, int, int,
+                             hipStream_t);
+int sample_topk_topp_max_vocab();
 void launch_moe_gemm(__hip_bfloat16*, const __hip_bfloat16*,
                      const __hip_bfloat16*, const int*, int, int, int, int,
                      bool, hipStream_t);
@@ -543,6 +548,61 @@ void sample_argmax(torch::Tensor out, torch::Tensor logits,
   });
 }
 
+void sample_topk_topp(torch::Tensor out, torch::Tensor logits,
+                      torch::Tensor temps, c10::optional<torch::Tensor> noise,
+                      torch::Tensor top_k, torch::Tensor top_p,
+                      c10::optional<torch::Tensor> kept) {
+  TORCH_CHECK(logits.dim() == 2 && logits.is_cuda() && logits.is_contiguous());
+  const int N = logits.size(0);
+  const long V = logits.size(1);
+  const auto dev = logits.device();
+  TORCH_CHECK(V >= 1 && V <= sample_topk_topp_max_vocab(),
+              "vocab out of range for sample_topk_topp");
+  TORCH_CHECK(out.scalar_type() == at::ScalarType::Long && out.dim() == 1 &&
+              out.size(0) == N && out.is_contiguous() && out.device() == dev);
+  TORCH_CHECK(temps.scalar_type() == at::ScalarType::Float &&
+              temps.dim() == 1 && temps.size(0) == N &&
+              temps.is_contiguous() && temps.device() == dev);
+  TORCH_CHECK(top_k.scalar_type() == at::ScalarType::Int && top_k.dim() == 1 &&
+              top_k.size(0) == N && top_k.is_contiguous() &&
+              top_k.device() == dev);
+  TORCH_CHECK(top_p.scalar_type() == at::ScalarType::Float &&
+              top_p.dim() == 1 && top_p.size(0) == N &&
+              top_p.is_contiguous() && top_p.device() == dev);
+  const float* np_ = nullptr;
+  if (noise.has_value()) {
+    TORCH_CHECK(noise->scalar_type() == at::ScalarType::Float &&
+                noise->is_contiguous() && noise->dim() == 2 &&
+                noise->size(0) == N && noise->size(1) == V &&
+                noise->device() == dev);
+    np_ = noise->data_ptr<float>();
+  }
+  int* kp = nullptr;
+  if (kept.has_value()) {
+    TORCH_CHECK(kept->scalar_type() == at::ScalarType::Int &&
+                kept->dim() == 1 && kept->size(0) == N &&
+                kept->is_contiguous() && kept->device() == dev);
+    kp = kept->data_ptr<int>();
+  }
+  if (N == 0) return;
+  switch (logits.scalar_type()) {
+    case at::ScalarType::BFloat16:
+      launch_sample_topk_topp<__hip_bfloat16>(
+          out.data_ptr<long>(), kp, cptr<__hip_bfloat16>(logits),
+          temps.data_ptr<float>(), np_, top_k.data_ptr<int>(),
+          top_p.data_ptr<float>(), N, (int)V, current_stream());
+      break;
+    case at::ScalarType::Half:
+      launch_sample_topk_topp<__half>(
+          out.data_ptr<long>(), kp, cptr<__half>(logits),
+          temps.data_ptr<float>(), np_, top_k.data_ptr<int>(),
+          top_p.data_ptr<float>(), N, (int)V, current_stream());
+      break;
+    default:
+      TORCH_CHECK(false, "sample_topk_topp serves bf16 / f16 logits only");
+  }
+}
+
 void logsoftmax_topk(torch::Tensor topv, torch::Tensor topi,
                      torch::Tensor chosen_lp, torch::Tensor ranks,
                      torch::Tensor logits, torch::Tensor chosen) {
@@ -613,6 +673,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused log-softmax + top-K + sampled-token rank (one HBM pass)");
   m.def("sample_argmax", &sample_argmax,
         "fused temperature/gumbel-race sampling + greedy argmax (CDNA4)");
+  m.def("sample_topk_topp", &sample_topk_topp,
+        "fused top-k / top-p sampling, radix-select cut + race (CDNA4)");
+  m.def("sample_topk_topp_max_vocab", &sample_topk_topp_max_vocab,
+        "largest vocab sample_topk_topp serves");
   m.def("lora_bgmv", &lora_bgmv,
         "batched multi-LoRA shrink+expand for mixed-adapter batches (CDNA4)");
 }

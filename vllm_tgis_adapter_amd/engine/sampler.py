@@ -7,8 +7,11 @@ on-device; the per-position logprob dicts the TGIS wire format needs
 (grpc_server.py:701-756) are assembled host-side from one batched top-k.
 
 Greedy and plain temperature-sampling rows take the fused HIP kernel
-(kernels/sampling.hip, exponential-race identity) in one pass; top-k/top-p,
-penalties, processors and logprob extraction run the vectorised torch path.
+(kernels/sampling.hip, exponential-race identity) in one pass; batches with
+top-k/top-p rows take its radix-select sibling
+(kernels/sampling_topk_topp.hip) when the logits are bf16/f16 on the GPU.
+Penalties, processors, guided masks, and top-k/top-p over f32 or CPU logits
+run the vectorised torch path.
 """
 
 from __future__ import annotations
@@ -94,8 +97,11 @@ class Sampler:
         """Launch the fused one-pass sampler WITHOUT host sync.
 
         Returns the device token-id tensor (caller syncs via .tolist()) when
-        every row is greedy or plain temperature sampling — no top-k/top-p,
-        penalties, processors or guided masks — else None.  Rows that
+        every row is greedy, plain temperature, or top-k/top-p sampling — no
+        penalties, processors or guided masks — else None.  Top-k/top-p
+        rows qualify only where the fused HIP sampler serves the logits
+        (bf16/f16 on the GPU); on CPU, under VTA_FORCE_REFERENCE, or with
+        f32 logits such a batch returns None as before.  Rows that
         request logprobs/top-N stay ON this path: their log-softmax / top-k
         / rank tensors are launched asynchronously here and synced later in
         ``finish_fused`` (the TGIS wire always wants top-N details, and
@@ -108,6 +114,8 @@ class Sampler:
         n, vocab = logits.shape
         simple = True
         any_sampling = False
+        any_filter = False  # some sampling row sets top-k / top-p
+        filter_ok = _ops.sample_topk_topp_usable(logits)
         ban_rows: list[int] = []  # rows with min_tokens pending: EOS banned
         ban_eos: list[int] = []
         lp_rows: list[int] = []   # rows that want logprob details (deferred)
@@ -132,8 +140,10 @@ class Sampler:
             if p.temperature != 0.0:
                 any_sampling = True
                 if not (p.top_k <= 0 or p.top_k >= vocab) or p.top_p < 1.0:
-                    simple = False
-                    break
+                    if not filter_ok:  # CPU / force-reference / f32 logits
+                        simple = False
+                        break
+                    any_filter = True
         if not simple:
             self._pending_lp = None
             return None
@@ -194,7 +204,19 @@ class Sampler:
         out = torch.empty(n, dtype=torch.long, device=logits.device)
         if _dbg:
             _tc = _time.perf_counter()
-        _ops.sample_argmax(out, logits, temps, noise)
+        if any_filter:
+            top_k = self._h2d_list(
+                "top_k",
+                [min(max(r.sampling_params.top_k, 0), vocab) for r in requests],
+                torch.int32,
+            )
+            top_p = self._h2d_list(
+                "top_p", [r.sampling_params.top_p for r in requests],
+                torch.float32,
+            )
+            _ops.sample_topk_topp(out, logits, temps, noise, top_k, top_p)
+        else:
+            _ops.sample_argmax(out, logits, temps, noise)
         if _dbg:
             _td = _time.perf_counter()
             d = self.__dict__.setdefault("_lt2", [0.0, 0.0, 0.0, 0])

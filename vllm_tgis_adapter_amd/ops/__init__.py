@@ -347,6 +347,33 @@ def sample_argmax(
     _C.sample_argmax(out, logits, temps, noise)
 
 
+def sample_topk_topp_usable(logits: torch.Tensor) -> bool:
+    """The fused top-k/top-p sampler serves contiguous 16-bit logits; f32
+    logits stay on the torch path."""
+    return (native_enabled(logits) and logits.dim() == 2
+            and logits.dtype in (torch.bfloat16, torch.float16)
+            and logits.is_contiguous()
+            and 1 <= logits.shape[1] <= _C.sample_topk_topp_max_vocab())
+
+
+def sample_topk_topp(
+    out: torch.Tensor,     # [N] int64
+    logits: torch.Tensor,  # [N, V] bf16 / f16, contiguous
+    temps: torch.Tensor,   # [N] float32, 0 = greedy (filters ignored)
+    noise: torch.Tensor | None,  # [N, V] float32 Exp(1) draws for temp>0 rows
+    top_k: torch.Tensor,   # [N] int32, <=0 or >=V = off
+    top_p: torch.Tensor,   # [N] float32, >=1 = off
+    kept: torch.Tensor | None = None,  # [N] int32 out: kept-set size
+) -> None:
+    """Fused top-k / top-p sampling for a mixed batch (E7): tokens ordered by
+    logit descending (ties: lower index first), the first
+    c = max(1, min(top_k, #{j : prefix-mass_j <= top_p})) are kept, and the
+    exponential race argmax(logits/T - log noise) runs over those.  ``kept``
+    receives c (V for greedy / unfiltered rows).  Launch only, no host sync."""
+    assert sample_topk_topp_usable(logits), "sample_topk_topp is the GPU path"
+    _C.sample_topk_topp(out, logits, temps, noise, top_k, top_p, kept)
+
+
 def logsoftmax_topk_usable(logits: torch.Tensor) -> bool:
     # V >= 2048 guarantees every lane feeds both accumulator pairs
     return (native_enabled(logits) and logits.dtype == torch.bfloat16
