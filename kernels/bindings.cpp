@@ -86,6 +86,13 @@ void launch_lora_shrink(float*, const T*, const T*, const int*, int, int, int,
 template <typename T>
 void launch_lora_expand(T*, const float*, const T*, const int*, const float*,
                         int, int, int, int, int, hipStream_t);
+int lora_sgmv_num_ksplit(int T, int K);
+void launch_lora_sgmv_shrink(float*, const __hip_bfloat16*,
+                             const __hip_bfloat16*, const int*, int, int, int,
+                             int, int, hipStream_t);
+void launch_lora_sgmv_expand(__hip_bfloat16*, const float*,
+                             const __hip_bfloat16*, const int*, const float*,
+                             int, int, int, int, int, int, int, hipStream_t);
 template <typename T>
 void launch_sample_argmax(long*, const T*, const float*, const float*, int,
                           int, hipStream_t);
@@ -503,6 +510,52 @@ void lora_bgmv(torch::Tensor out, torch::Tensor x, torch::Tensor a_stack,
   });
 }
 
+// tmp is the shrink's K-split workspace [lora_sgmv_num_ksplit(T, K), T, Rpad]
+// f32 with Rpad = R rounded up to 16.  ops.lora_sgmv_usable states the shape
+// conditions for callers; the checks here only guard the kernels' indexing.
+void lora_sgmv(torch::Tensor out, torch::Tensor x, torch::Tensor a_stack,
+               torch::Tensor b_stack, torch::Tensor tmp, torch::Tensor slots,
+               torch::Tensor scales, int64_t off) {
+  const int Tn = x.size(0);
+  const int K = x.size(1);
+  const int L = a_stack.size(0);
+  const int R = a_stack.size(1);
+  const int N = b_stack.size(1);
+  const int out_w = out.size(1);
+  const int S = lora_sgmv_num_ksplit(Tn, K);
+  const int Rpad = (R + 15) / 16 * 16;
+  TORCH_CHECK(x.dim() == 2 && out.dim() == 2 && a_stack.dim() == 3 &&
+              b_stack.dim() == 3 && tmp.dim() == 3);
+  TORCH_CHECK(x.scalar_type() == at::ScalarType::BFloat16 &&
+              out.scalar_type() == at::ScalarType::BFloat16 &&
+              a_stack.scalar_type() == at::ScalarType::BFloat16 &&
+              b_stack.scalar_type() == at::ScalarType::BFloat16);
+  TORCH_CHECK(slots.scalar_type() == at::ScalarType::Int &&
+              tmp.scalar_type() == at::ScalarType::Float &&
+              scales.scalar_type() == at::ScalarType::Float);
+  TORCH_CHECK(x.is_contiguous() && out.is_contiguous() &&
+              a_stack.is_contiguous() && b_stack.is_contiguous() &&
+              tmp.is_contiguous() && slots.is_contiguous() &&
+              scales.is_contiguous());
+  for (const torch::Tensor& t : {x, out, a_stack, b_stack, tmp})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0);
+  TORCH_CHECK(out.size(0) == Tn && slots.numel() == Tn);
+  TORCH_CHECK(a_stack.size(2) == K && b_stack.size(0) == L &&
+              b_stack.size(2) == R && scales.numel() == L);
+  TORCH_CHECK(tmp.size(0) == S && tmp.size(1) == Tn && tmp.size(2) == Rpad);
+  TORCH_CHECK(L >= 1 && R >= 1 && R <= 64 && K >= 128 && K % 128 == 0);
+  TORCH_CHECK(N >= 32 && N % 32 == 0 && off >= 0 && off % 8 == 0 &&
+              out_w % 8 == 0 && off + N <= out_w);
+  if (Tn == 0) return;
+  launch_lora_sgmv_shrink(tmp.data_ptr<float>(), cptr<__hip_bfloat16>(x),
+                          cptr<__hip_bfloat16>(a_stack), slots.data_ptr<int>(),
+                          Tn, R, K, L, S, current_stream());
+  launch_lora_sgmv_expand(ptr<__hip_bfloat16>(out), tmp.data_ptr<float>(),
+                          cptr<__hip_bfloat16>(b_stack), slots.data_ptr<int>(),
+                          scales.data_ptr<float>(), Tn, R, N, out_w, (int)off,
+                          L, S, current_stream());
+}
+
 void moe_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
               torch::Tensor seg_off, bool gated) {
   const int T = x.size(0);
@@ -679,4 +732,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "largest vocab sample_topk_topp serves");
   m.def("lora_bgmv", &lora_bgmv,
         "batched multi-LoRA shrink+expand for mixed-adapter batches (CDNA4)");
+  m.def("lora_sgmv", &lora_sgmv,
+        "segmented multi-LoRA shrink+expand for prefill batches (CDNA4 MFMA)");
+  m.def("lora_sgmv_num_ksplit", &lora_sgmv_num_ksplit,
+        "K-split of the lora_sgmv shrink grid (pure function of shapes)");
 }

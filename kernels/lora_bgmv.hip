@@ -12,8 +12,9 @@
 //   expand: R <= 64 fits a lane-resident tmp row; each thread owns one
 //           output column and walks r with the B row loads coalesced.
 // Decode batches are tiny (T <= a few hundred) and A/B stay L2-resident, so
-// per-token re-reads are cheap; grouping tokens by adapter (true SGMV) only
-// pays at prefill sizes, where the torch grouped path still applies.
+// per-token re-reads are cheap; grouping tokens by adapter only pays at
+// prefill sizes, which the segmented MFMA kernels in lora_sgmv.hip serve
+// (bf16; engine/lora.apply_lora picks by token count).
 
 #include "common.h"
 

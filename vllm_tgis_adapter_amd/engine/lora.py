@@ -5,9 +5,11 @@ onto the serving model and applies them per request in mixed batches.
 
 Application model: each step batch carries a per-token adapter id; for every
 active adapter the delta  x @ A^T @ B^T * (alpha/r)  is added onto the
-matching projection outputs.  Today this runs as batched torch GEMMs grouped
-by adapter (shrink+expand per adapter — fine for a handful of live adapters);
-the batched SGMV HIP kernel replaces the inner loop next.
+matching projection outputs.  On the GPU this is native HIP over stacked,
+rank-padded weights and a per-token slot: the BGMV kernels (one workgroup per
+token) for decode-sized batches, the segmented MFMA kernels (ops.lora_sgmv,
+adapters resolved per 32-token tile inside the kernel) for prefill-sized bf16
+batches.  CPU tensors run torch GEMMs grouped by adapter.
 
 TP sharding follows the base layer: column-parallel projections
 (q/k/v/gate/up) shard B on the output dim; row-parallel projections (o/down)
@@ -59,6 +61,15 @@ CTX = LoRAContext()
 
 # (slot_ids, layer, proj, N, dtype) -> (a_stack, b_stack, scales) for lora_bgmv
 _STACK_CACHE: dict = {}
+
+# Batches of at least this many tokens take the segmented MFMA kernels
+# (ops.lora_sgmv) where they apply; smaller ones stay on BGMV.  SGMV wins on
+# prefill-like slots from the smallest size measured, but the dispatch sees
+# only T and a slot per token at rank 16 is slower on it up to T=512, so the
+# threshold is the first measured T a pure decode step (<= max_num_seqs = 256
+# tokens) cannot reach: profiles/r04_lora_sgmv.txt.  VTA_LORA_SGMV_MIN_T
+# overrides it.
+_SGMV_MIN_T = 512
 
 
 def invalidate_adapter(lora_int_id: int) -> None:
@@ -155,13 +166,18 @@ def apply_lora(
         and x.shape[1] % 8 == 0
         and all(a.rank <= 64 for a in CTX.adapters.values())
     ):
+        sgmv = x.shape[0] >= int(
+            os.environ.get("VTA_LORA_SGMV_MIN_T", _SGMV_MIN_T))
         for name, start, end in projs:
             stacks = _get_stacks(layer_idx, name, end - start, x.shape[1],
                                  x.dtype, x.device)
             if stacks is None:
                 continue
             a_stack, b_stack, scales = stacks
-            ops.lora_bgmv(out, x, a_stack, b_stack, CTX.token_slots, scales, start)
+            if sgmv and ops.lora_sgmv_usable(x, out, a_stack, b_stack, start):
+                ops.lora_sgmv(out, x, a_stack, b_stack, CTX.token_slots, scales, start)
+            else:
+                ops.lora_bgmv(out, x, a_stack, b_stack, CTX.token_slots, scales, start)
         return out
     token_ids = CTX.token_lora_ids
     for lora_id, adapter in CTX.adapters.items():

@@ -336,6 +336,54 @@ def lora_bgmv(
     _C.lora_bgmv(out, x, a_stack, b_stack, tmp, slots, scales, off)
 
 
+def lora_sgmv_usable(
+    x: torch.Tensor,        # [T, K]
+    out: torch.Tensor,      # [T, out_w]
+    a_stack: torch.Tensor,  # [L, R, K]
+    b_stack: torch.Tensor,  # [L, N, R]
+    off: int,
+) -> bool:
+    """The segmented MFMA LoRA path serves contiguous, 16-byte-aligned bf16
+    with rank <= 64.  K % 128: the four waves of a shrink workgroup split K into whole 32-k MFMA
+    steps of 16-byte fragment loads.  N % 32, off % 8, out_w % 8: the expand
+    updates ``out`` in 16-byte pieces of 8 columns, two interleaved 16-row
+    n-blocks at a time.  Everything else stays on lora_bgmv."""
+    if not (native_enabled(x) and x.dim() == 2 and out.dim() == 2
+            and a_stack.dim() == 3 and b_stack.dim() == 3):
+        return False
+    if any(t.dtype != torch.bfloat16 or not t.is_contiguous()
+           or t.data_ptr() % 16 != 0 for t in (x, out, a_stack, b_stack)):
+        return False
+    k, r, n, out_w = x.shape[1], a_stack.shape[1], b_stack.shape[1], out.shape[1]
+    return (x.shape[0] >= 1 and 1 <= r <= 64
+            and k >= 128 and k % 128 == 0
+            and n >= 32 and n % 32 == 0
+            and off >= 0 and off % 8 == 0 and out_w % 8 == 0)
+
+
+def lora_sgmv(
+    out: torch.Tensor,      # [T, out_w] updated in place
+    x: torch.Tensor,        # [T, K]
+    a_stack: torch.Tensor,  # [L, R, K]
+    b_stack: torch.Tensor,  # [L, N, R]
+    slots: torch.Tensor,    # [T] int32, -1 = no adapter
+    scales: torch.Tensor,   # [L] float32
+    off: int,
+) -> None:
+    """lora_bgmv's contract on the segmented MFMA kernels for prefill-sized
+    batches: tokens are grouped by adapter inside the kernel (no sort, no host
+    sync), the shrink's K-split partials are summed in fixed order so results
+    repeat bit-for-bit.  Launch only."""
+    assert lora_sgmv_usable(x, out, a_stack, b_stack, off), \
+        "lora_sgmv needs lora_sgmv_usable(); lora_bgmv serves the rest"
+    t, k = x.shape
+    tmp = torch.empty(
+        (_C.lora_sgmv_num_ksplit(t, k), t, (a_stack.shape[1] + 15) // 16 * 16),
+        dtype=torch.float32, device=x.device,
+    )
+    _C.lora_sgmv(out, x, a_stack, b_stack, tmp, slots, scales, off)
+
+
 def sample_argmax(
     out: torch.Tensor,     # [N] int64
     logits: torch.Tensor,  # [N, V]
