@@ -5,24 +5,43 @@
 // (rocprofv3 r1: 155 us/call vs a ~17 us HBM roofline at batch 64, ctx 512).
 // Here Q·K^T runs on v_mfma_f32_32x32x16_bf16 tiles with the swapped-operand
 // trick from the prefill kernel (S^T = K·Q^T, so softmax stats are per-lane
-// column with ONE shfl per 32-slot tile), P is repacked with
-// v_cvt_pk_bf16_f32 + v_permlane32_swap into the P·V A-operand, and V tiles
-// are staged per-wave through LDS so the transposed B-fragment gather stays
-// on-chip.
+// column with ONE shfl per 32-slot tile), and P is repacked with
+// v_cvt_pk_bf16_f32 + v_permlane32_swap into the P·V A-operand.
+//
+// Memory side (the kernel is a KV stream: 2 bytes per K and V element, once):
+//   * K and V rows are both fetched 16 lanes across one contiguous row, so
+//     every load instruction covers whole cache lines, and both are staged
+//     through a per-wave LDS image (no barriers: a wave only ever touches its
+//     own image, and LDS operations of one wave execute in order).
+//   * The loop is software-pipelined: tile t+1's global loads are issued
+//     right after tile t's registers have been written to LDS and stay in
+//     flight under tile t's QK^T, softmax and PV.
+//   * K image: [32][HEAD_DIM] bf16 with byte ^= ((row & m) << 4) so the
+//     ds_read_b128 A-fragment reads (one row per lane) are conflict-free.
+//   * V image: HEAD_DIM/16 subtiles [32 kv][16 d] row-major, 1152 B apart,
+//     read as B fragments with the hardware transpose ds_read_b64_tr_b16
+//     (same layout as attention_prefill_mfma_v2.hip).
+//   * The accumulator rescale (16 cross-lane shuffles + 16*DT multiplies) is
+//     skipped for tiles in which no column's running max moved; the factor
+//     is exactly 1.0 there, so results are unchanged.
 //
 // Flash-decoding split: grid (nseq, kvh, npart); the context is cut into
 // npart contiguous tile ranges and each workgroup's 4 waves take tiles
-// round-robin inside their range.  Every wave writes an independent partial
-// (m, l, acc_f32) — no cross-wave merge in this kernel — and a small merge
-// kernel reduces the npart*4 partials per (seq, head).  npart is a pure
-// function of tensor shapes, so the launch is hipGraph-stable while the
-// in-kernel split adapts to the runtime seq_len.
+// round-robin inside their range.  With npart > 1 every wave writes an
+// independent partial (m, l, acc_f32) and a small merge kernel reduces the
+// npart*4 partials per (seq, head).  With npart == 1 (every batch that fills
+// the device on its own) the four waves merge through LDS with the same
+// arithmetic and write bf16 `out` directly: no partials traffic, no second
+// launch.  npart is a pure function of tensor shapes, so the launch is
+// hipGraph-stable while the in-kernel split adapts to the runtime seq_len.
 
 #include "common.h"
 #include <float.h>
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_d;
+typedef __attribute__((address_space(3))) bf16x4_d* lds_tr_ptr_d;
 
 // 8 consecutive KV elements as bf16: direct for bf16 caches, hardware
 // cvt_pk_f32_fp8 for e4m3 caches (fp8 KV halves the decode HBM stream)
@@ -40,9 +59,12 @@ DEVINLINE bf16x8_t load_kv8<unsigned char>(const unsigned char* p) {
 
 #define KVT 32     // kv slots per mfma tile
 #define NWAVES 4   // waves per workgroup
+#define MAX_GROUP 8
+#define VSUB_BYTES 1152  // one [32 kv][16 d] V subtile + 128 B bank pad
 
-template <int HEAD_DIM, typename CT>
+template <int HEAD_DIM, typename CT, bool DIRECT>
 __global__ __launch_bounds__(256, 2) void paged_decode_mfma_kernel(
+    __hip_bfloat16* __restrict__ out,  // [nseq, nheads, HD] (DIRECT only)
     float* __restrict__ part_acc,   // [nseq, nheads, P, HEAD_DIM] f32
     float* __restrict__ part_ml,    // [nseq, nheads, P, 2] f32 (m, l)
     const __hip_bfloat16* __restrict__ q,        // [nseq, nheads, HD]
@@ -58,6 +80,14 @@ __global__ __launch_bounds__(256, 2) void paged_decode_mfma_kernel(
     const int max_blocks) {
   constexpr int KCH = HEAD_DIM / 16;  // k-chunks for the QK^T mfma
   constexpr int DT = HEAD_DIM / 32;   // 32-col output tiles
+  constexpr int ROW_BYTES = HEAD_DIM * 2;
+  constexpr int K_SWZ = ROW_BYTES / 16 - 1;  // row bits folded into the 16-B slot
+  constexpr int K_BYTES = KVT * ROW_BYTES;
+  constexpr int V_BYTES = (HEAD_DIM / 16) * VSUB_BYTES;
+  constexpr int WAVE_LDS = K_BYTES + V_BYTES;
+  static_assert(NWAVES * WAVE_LDS >=
+                    NWAVES * MAX_GROUP * (HEAD_DIM + 2) * (int)sizeof(float),
+                "the wave-merge scratch aliases the staging images");
 
   const int seq = blockIdx.x;
   const int kv_head = blockIdx.y;
@@ -81,9 +111,10 @@ __global__ __launch_bounds__(256, 2) void paged_decode_mfma_kernel(
   const int* btable = block_tables + (long)seq * max_blocks;
   const long kv_row_stride = (long)kvh * HEAD_DIM;
 
-  // per-wave V staging tile (linear; the B gather reads rows across lanes)
-  __shared__ __hip_bfloat16 v_lds_all[NWAVES * KVT * HEAD_DIM];
-  __hip_bfloat16* v_lds = v_lds_all + wave * KVT * HEAD_DIM;
+  // per-wave K and V staging images
+  __shared__ __attribute__((aligned(16))) char lds_all[NWAVES * WAVE_LDS];
+  char* k_lds = lds_all + wave * WAVE_LDS;
+  char* v_lds = k_lds + K_BYTES;
 
   // ---- Q as B fragments: lane holds Q[q=col][ks*16 + half*8 + j] ---------
   bf16x8_t qb[KCH];
@@ -103,64 +134,64 @@ __global__ __launch_bounds__(256, 2) void paged_decode_mfma_kernel(
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) acc_o[dt] = f32x16_t{};
 
-  constexpr int VPASS = KVT * HEAD_DIM / 8 / 64;  // V staging passes per wave
+  // staging map, same for K and V: LPR lanes across one row, 64/LPR rows per
+  // pass.  Slots at or past seq_len are never dereferenced (neither the block
+  // table entry nor the cache row) and stage zeros.
+  constexpr int LPR = HEAD_DIM / 8;        // lanes per row
+  constexpr int ROWS_PER_PASS = 64 / LPR;  // rows per pass per wave
+  constexpr int NPASS = KVT / ROWS_PER_PASS;
+  const int st_row = lane / LPR;
+  const int st_d8 = (lane % LPR) * 8;
+  bf16x8_t st_k[NPASS], st_v[NPASS];
 
-  for (int t = tile_lo + wave; t < tile_hi; t += NWAVES) {
-    const int kv_base = t * KVT;
-
-    // ---- issue ALL of this tile's HBM loads first (K frags + V rows) -----
-    // K is needed first (QK^T mfma), so its 8 loads go out before V's; the
-    // mfma chain then only waits on vmcnt covering K while V stays in
-    // flight, and the V->LDS writes drain afterwards.  Keeping every load
-    // of the tile outstanding together (instead of load->ds_write per
-    // pass) collapses ~9 HBM round trips per tile into ~1.
-    bf16x8_t ka[KCH];
-    {
-      const int pos = kv_base + col;
+  auto issue_loads = [&](int t) {
+#pragma unroll
+    for (int pass = 0; pass < NPASS; ++pass) {
+      const int pos = t * KVT + pass * ROWS_PER_PASS + st_row;
+      st_k[pass] = bf16x8_t{};
+      st_v[pass] = bf16x8_t{};
       if (pos < seq_len) {
         const int block = btable[pos / block_size];
-        const CT* k_row =
-            k_cache + ((long)block * block_size + pos % block_size) * kv_row_stride +
-            (long)kv_head * HEAD_DIM;
-#pragma unroll
-        for (int ks = 0; ks < KCH; ++ks)
-          ka[ks] = load_kv8<CT>(k_row + ks * 16 + half * 8);
-      } else {
-#pragma unroll
-        for (int ks = 0; ks < KCH; ++ks) ka[ks] = bf16x8_t{};
+        const long row = ((long)block * block_size + pos % block_size) *
+                             kv_row_stride +
+                         (long)kv_head * HEAD_DIM + st_d8;
+        st_k[pass] = load_kv8<CT>(k_cache + row);
+        st_v[pass] = load_kv8<CT>(v_cache + row);
       }
     }
-    bf16x8_t vv[VPASS];
-    {
-      constexpr int LPR = HEAD_DIM / 8;        // lanes per row
-      constexpr int ROWS_PER_PASS = 64 / LPR;  // rows per pass per wave
-      const int r_in_pass = lane / LPR;
-      const int d8 = (lane % LPR) * 8;
+  };
+
+  int t = tile_lo + wave;
+  if (t < tile_hi) issue_loads(t);
+
+  for (; t < tile_hi; t += NWAVES) {
+    const int kv_base = t * KVT;
+
+    // ---- tile t: registers -> LDS images ---------------------------------
 #pragma unroll
-      for (int pass = 0; pass < VPASS; ++pass) {
-        const int s = pass * ROWS_PER_PASS + r_in_pass;
-        const int pos = kv_base + s;
-        vv[pass] = bf16x8_t{};
-        if (pos < seq_len) {
-          const int block = btable[pos / block_size];
-          const long row = ((long)block * block_size + pos % block_size) *
-                               kv_row_stride +
-                           (long)kv_head * HEAD_DIM + d8;
-          vv[pass] = load_kv8<CT>(v_cache + row);
-        }
-      }
-#pragma unroll
-      for (int pass = 0; pass < VPASS; ++pass) {
-        const int s = pass * ROWS_PER_PASS + r_in_pass;
-        *reinterpret_cast<bf16x8_t*>(v_lds + s * HEAD_DIM + d8) = vv[pass];
-      }
+    for (int pass = 0; pass < NPASS; ++pass) {
+      const int s = pass * ROWS_PER_PASS + st_row;
+      *reinterpret_cast<bf16x8_t*>(
+          k_lds + s * ROW_BYTES + ((st_d8 * 2) ^ ((s & K_SWZ) << 4))) = st_k[pass];
     }
+#pragma unroll
+    for (int pass = 0; pass < NPASS; ++pass) {
+      const int s = pass * ROWS_PER_PASS + st_row;
+      *reinterpret_cast<bf16x8_t*>(
+          v_lds + (st_d8 >> 4) * VSUB_BYTES + s * 32 + (st_d8 & 15) * 2) = st_v[pass];
+    }
+
+    // ---- tile t+NWAVES: loads go out now, land under this tile's math ----
+    if (t + NWAVES < tile_hi) issue_loads(t + NWAVES);
 
     // ---- S^T = K · Q^T ---------------------------------------------------
     f32x16_t acc_s{};
 #pragma unroll
-    for (int ks = 0; ks < KCH; ++ks)
-      acc_s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka[ks], qb[ks], acc_s, 0, 0, 0);
+    for (int ks = 0; ks < KCH; ++ks) {
+      const bf16x8_t ka = *reinterpret_cast<const bf16x8_t*>(
+          k_lds + col * ROW_BYTES + ((ks * 32 + half * 16) ^ ((col & K_SWZ) << 4)));
+      acc_s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka, qb[ks], acc_s, 0, 0, 0);
+    }
 
     // ---- online softmax (stats per q col = this lane's col) --------------
     float s_val[16];
@@ -175,6 +206,7 @@ __global__ __launch_bounds__(256, 2) void paged_decode_mfma_kernel(
     }
     const float tile_max = fmaxf(local_max, __shfl_xor(local_max, 32, 64));
     const float m_new = fmaxf(m_state, tile_max);
+    const bool max_moved = m_new > m_state;
     const float rescale = __expf(m_state - m_new);
     m_state = m_new;
 
@@ -187,17 +219,20 @@ __global__ __launch_bounds__(256, 2) void paged_decode_mfma_kernel(
     }
     l_state = l_state * rescale + local_sum + __shfl_xor(local_sum, 32, 64);
 
-    // rescale factors redistributed to the PV accumulator's q rows
-    float f_reg[16];
+    // rescale factors redistributed to the PV accumulator's q rows; when no
+    // column's max moved every factor is exactly 1.0 and the pass is skipped
+    if (__any(max_moved)) {
+      float f_reg[16];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
-      f_reg[r] = __shfl(rescale, qrow, 64);
-    }
+      for (int r = 0; r < 16; ++r) {
+        const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
+        f_reg[r] = __shfl(rescale, qrow, 64);
+      }
 #pragma unroll
-    for (int dt = 0; dt < DT; ++dt) {
+      for (int dt = 0; dt < DT; ++dt) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc_o[dt][r] *= f_reg[r];
+        for (int r = 0; r < 16; ++r) acc_o[dt][r] *= f_reg[r];
+      }
     }
 
     // ---- pack P to bf16 A-fragments (cvt_pk + permlane32_swap) -----------
@@ -224,36 +259,78 @@ __global__ __launch_bounds__(256, 2) void paged_decode_mfma_kernel(
     }
 
     // ---- PV: out[q][d] += P[q][kv] V[kv][d] ------------------------------
+    // B fragment: lane needs V[c*16 + half*8 + j][dt*32 + col], j = 0..7.
+    // Each 16-lane quarter transposes a [4 kv][16 d] window per read.
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
+      const char* sub = v_lds + (dt * 2 + (col >> 4)) * VSUB_BYTES + (lane & 15) * 8;
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        bf16x8_t b;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          b[j] = *reinterpret_cast<const short*>(
-              v_lds + (c * 16 + half * 8 + j) * HEAD_DIM + dt * 32 + col);
-        acc_o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[c], b, acc_o[dt], 0, 0, 0);
+        const char* w = sub + (c * 16 + half * 8) * 32;
+        union { bf16x4_d h[2]; bf16x8_t v; } b;
+        b.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_tr_ptr_d)w);
+        b.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_tr_ptr_d)(w + 128));
+        acc_o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa[c], b.v, acc_o[dt], 0, 0, 0);
       }
     }
   }
 
-  // ---- per-wave partial store: (m, l) per q col + f32 accumulator --------
-  const int P = npart * NWAVES;
-  const int pw = part * NWAVES + wave;
-  if (lane < group) {
-    float* ml = part_ml + (((long)seq * nheads + head0 + lane) * P + pw) * 2;
-    ml[0] = m_state;
-    ml[1] = l_state;
-  }
+  if constexpr (DIRECT) {
+    // ---- npart == 1: merge the four waves through LDS, write bf16 out ----
+    // Same arithmetic, in the same order, as decode_merge_kernel over P = 4.
+    float* mg_acc = reinterpret_cast<float*>(lds_all);  // [NWAVES][8][HD]
+    float* mg_ml = mg_acc + NWAVES * MAX_GROUP * HEAD_DIM;  // [NWAVES][8][2]
+    __syncthreads();  // every wave is done with its staging images
+    if (lane < group) {
+      mg_ml[(wave * MAX_GROUP + lane) * 2 + 0] = m_state;
+      mg_ml[(wave * MAX_GROUP + lane) * 2 + 1] = l_state;
+    }
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
-    if (qrow >= group) continue;
-    float* acc_row =
-        part_acc + (((long)seq * nheads + head0 + qrow) * P + pw) * HEAD_DIM;
+    for (int r = 0; r < 16; ++r) {
+      const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
+      if (qrow >= group) continue;
 #pragma unroll
-    for (int dt = 0; dt < DT; ++dt) acc_row[dt * 32 + col] = acc_o[dt][r];
+      for (int dt = 0; dt < DT; ++dt)
+        mg_acc[(wave * MAX_GROUP + qrow) * HEAD_DIM + dt * 32 + col] = acc_o[dt][r];
+    }
+    __syncthreads();
+    for (int e = tid; e < group * HEAD_DIM; e += NWAVES * 64) {
+      const int h = e / HEAD_DIM;
+      const int d = e % HEAD_DIM;
+      float M = -FLT_MAX;
+#pragma unroll
+      for (int w = 0; w < NWAVES; ++w)
+        M = fmaxf(M, mg_ml[(w * MAX_GROUP + h) * 2]);
+      float L = 0.f, A = 0.f;
+#pragma unroll
+      for (int w = 0; w < NWAVES; ++w) {
+        const float f = __expf(mg_ml[(w * MAX_GROUP + h) * 2] - M);
+        // explicit fma: the merge kernel's loop compiles to fused ops, and
+        // both paths must round alike
+        L = __builtin_fmaf(f, mg_ml[(w * MAX_GROUP + h) * 2 + 1], L);
+        A = __builtin_fmaf(f, mg_acc[(w * MAX_GROUP + h) * HEAD_DIM + d], A);
+      }
+      const float inv = L > 0.f ? 1.f / L : 0.f;
+      out[((long)seq * nheads + head0 + h) * HEAD_DIM + d] = __float2bfloat16(A * inv);
+    }
+  } else {
+    // ---- per-wave partial store: (m, l) per q col + f32 accumulator ------
+    const int P = npart * NWAVES;
+    const int pw = part * NWAVES + wave;
+    if (lane < group) {
+      float* ml = part_ml + (((long)seq * nheads + head0 + lane) * P + pw) * 2;
+      ml[0] = m_state;
+      ml[1] = l_state;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int qrow = (r & 3) + 8 * (r >> 2) + 4 * half;
+      if (qrow >= group) continue;
+      float* acc_row =
+          part_acc + (((long)seq * nheads + head0 + qrow) * P + pw) * HEAD_DIM;
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) acc_row[dt * 32 + col] = acc_o[dt][r];
+    }
   }
 }
 
@@ -296,6 +373,31 @@ int decode_mfma_num_partitions(int nseq, int kvh, int max_context) {
   return npart;
 }
 
+template <int HEAD_DIM, typename CT>
+static void launch_decode_hd(__hip_bfloat16* out, float* part_acc,
+                             float* part_ml, const __hip_bfloat16* q,
+                             const CT* kc, const CT* vc, const int* bt,
+                             const int* sl, float scale, int nseq, int nheads,
+                             int kvh, int block_size, int max_blocks,
+                             int npart, hipStream_t stream) {
+  const int group = nheads / kvh;
+  dim3 grid(nseq, kvh, npart);
+  dim3 block(NWAVES * 64);
+  if (npart == 1) {
+    // part_acc / part_ml are not touched on this path
+    hipLaunchKernelGGL((paged_decode_mfma_kernel<HEAD_DIM, CT, true>), grid,
+                       block, 0, stream, out, part_acc, part_ml, q, kc, vc, bt,
+                       sl, scale, nheads, kvh, group, block_size, max_blocks);
+    return;
+  }
+  hipLaunchKernelGGL((paged_decode_mfma_kernel<HEAD_DIM, CT, false>), grid,
+                     block, 0, stream, out, part_acc, part_ml, q, kc, vc, bt,
+                     sl, scale, nheads, kvh, group, block_size, max_blocks);
+  hipLaunchKernelGGL(decode_merge_kernel<HEAD_DIM>, dim3(nseq, nheads),
+                     dim3(HEAD_DIM), 0, stream, out, part_acc, part_ml, nheads,
+                     npart * NWAVES);
+}
+
 template <typename CT>
 static void launch_decode_ct(__hip_bfloat16* out, float* part_acc,
                              float* part_ml, const __hip_bfloat16* q,
@@ -303,25 +405,16 @@ static void launch_decode_ct(__hip_bfloat16* out, float* part_acc,
                              const int* sl, float scale, int nseq, int nheads,
                              int kvh, int head_dim, int block_size,
                              int max_blocks, int npart, hipStream_t stream) {
-  const int group = nheads / kvh;
-  dim3 grid(nseq, kvh, npart);
-  dim3 block(256);
-  dim3 mgrid(nseq, nheads);
-  const int P = npart * NWAVES;
   switch (head_dim) {
     case 64:
-      hipLaunchKernelGGL((paged_decode_mfma_kernel<64, CT>), grid, block, 0,
-                         stream, part_acc, part_ml, q, kc, vc, bt, sl, scale,
-                         nheads, kvh, group, block_size, max_blocks);
-      hipLaunchKernelGGL(decode_merge_kernel<64>, mgrid, dim3(64), 0, stream,
-                         out, part_acc, part_ml, nheads, P);
+      launch_decode_hd<64, CT>(out, part_acc, part_ml, q, kc, vc, bt, sl, scale,
+                               nseq, nheads, kvh, block_size, max_blocks, npart,
+                               stream);
       break;
     case 128:
-      hipLaunchKernelGGL((paged_decode_mfma_kernel<128, CT>), grid, block, 0,
-                         stream, part_acc, part_ml, q, kc, vc, bt, sl, scale,
-                         nheads, kvh, group, block_size, max_blocks);
-      hipLaunchKernelGGL(decode_merge_kernel<128>, mgrid, dim3(128), 0, stream,
-                         out, part_acc, part_ml, nheads, P);
+      launch_decode_hd<128, CT>(out, part_acc, part_ml, q, kc, vc, bt, sl,
+                                scale, nseq, nheads, kvh, block_size,
+                                max_blocks, npart, stream);
       break;
     default:
       abort();

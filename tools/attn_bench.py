@@ -28,6 +28,16 @@ def bench(fn, iters=50):
     return t0.elapsed_time(t1) / iters * 1e3  # us
 
 
+def copy_probe_tbps(nbytes):
+    """Memory ceiling for a decode case: a plain device copy of a buffer the
+    size of the case's KV stream, timed like the kernel.  Counts the bytes
+    read plus the bytes written."""
+    src = torch.empty(nbytes, dtype=torch.uint8, device="cuda").fill_(1)
+    dst = torch.empty_like(src)
+    us = bench(lambda: dst.copy_(src))
+    return 2 * nbytes / us / 1e6
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kvh", type=int, default=8)
@@ -62,7 +72,8 @@ def main():
         print(name, out[name], flush=True)
 
     decode_cases = [("decode 256x576", 256, 576), ("decode 64x512", 64, 512),
-                ("decode 512x576", 512, 576), ("decode 512x1024", 512, 1024)]
+                    ("decode 512x544", 512, 544), ("decode 512x576", 512, 576),
+                    ("decode 512x800", 512, 800), ("decode 512x1024", 512, 1024)]
     if args.only == "prefill":
         decode_cases = []
     for name, nseq, ctx in decode_cases:
@@ -74,9 +85,14 @@ def main():
         sl = torch.full((nseq,), ctx, dtype=torch.int32, device="cuda")
         us = bench(lambda: ops.paged_attention_decode(
             q, kc, vc, tables, sl, args.hd ** -0.5, ctx))
-        kv_mb = nseq * ctx * args.kvh * args.hd * 2 * 2 * 2 / 1e6
-        out[name] = {"us": round(us, 1), "KV_MB": round(kv_mb, 1),
-                     "TBps": round(kv_mb / 1e3 / us * 1e3, 2)}
+        # K and V are each read once at 2 bytes per element
+        kv_bytes = nseq * ctx * args.kvh * args.hd * 2 * 2
+        tbps = kv_bytes / us / 1e6
+        del kc, vc
+        probe = copy_probe_tbps(kv_bytes)
+        out[name] = {"us": round(us, 1), "KV_MB": round(kv_bytes / 1e6, 1),
+                     "TBps": round(tbps, 2), "copy_probe_TBps": round(probe, 2),
+                     "of_probe": round(tbps / probe, 2)}
         print(name, out[name], flush=True)
 
     print(json.dumps(out))
