@@ -80,6 +80,16 @@ void launch_paged_decode_mfma(__hip_bfloat16*, float*, float*,
                               const __hip_bfloat16*, const int*, const int*,
                               float, int, int, int, int, int, int, int,
                               hipStream_t);
+void launch_paged_multiq_mfma(__hip_bfloat16*, float*, float*,
+                              const __hip_bfloat16*, const __hip_bfloat16*,
+                              const __hip_bfloat16*, const int*, const int*,
+                              const int*, float, int, int, int, int, int, int,
+                              int, int, int, hipStream_t);
+void launch_paged_multiq_mfma_fp8(__hip_bfloat16*, float*, float*,
+                                  const __hip_bfloat16*, const unsigned char*,
+                                  const unsigned char*, const int*, const int*,
+                                  const int*, float, int, int, int, int, int,
+                                  int, int, int, int, hipStream_t);
 template <typename T>
 void launch_lora_shrink(float*, const T*, const T*, const int*, int, int, int,
                         hipStream_t);
@@ -350,6 +360,84 @@ void paged_attention_prefill(torch::Tensor out, torch::Tensor q,
         (float)scale, nseq, nheads, kvh, head_dim, block_size, max_blocks,
         (int)max_query_len, current_stream());
   });
+}
+
+// Short query chunks over a long cached context (speculative verify): every
+// sequence's q_len * group query rows ride one pass over its KV stream.
+// ops.paged_attention_multiq_usable states the shape contract checked here.
+void paged_attention_multiq(torch::Tensor out, torch::Tensor q,
+                            torch::Tensor k_cache, torch::Tensor v_cache,
+                            torch::Tensor block_tables,
+                            torch::Tensor query_start_loc,
+                            torch::Tensor seq_lens, double scale,
+                            int64_t max_query_len) {
+  TORCH_CHECK(q.is_cuda() && q.dim() == 3 && k_cache.dim() == 4 &&
+                  block_tables.dim() == 2,
+              "q [T, heads, hd], caches [nb, bs, kvh, hd], tables [nseq, mb]");
+  const int nseq = seq_lens.numel();
+  const int total_tokens = q.size(0);
+  const int nheads = q.size(1);
+  const int head_dim = q.size(2);
+  const int kvh = k_cache.size(2);
+  const int block_size = k_cache.size(1);
+  const int max_blocks = block_tables.size(1);
+  const bool kv_fp8 = k_cache.scalar_type() == at::ScalarType::Byte;
+  TORCH_CHECK(q.scalar_type() == at::ScalarType::BFloat16 &&
+                  out.scalar_type() == at::ScalarType::BFloat16,
+              "multiq attention takes bf16 q and out");
+  TORCH_CHECK((kv_fp8 || k_cache.scalar_type() == at::ScalarType::BFloat16) &&
+                  v_cache.scalar_type() == k_cache.scalar_type(),
+              "multiq attention takes bf16 or e4m3 (uint8) KV caches");
+  TORCH_CHECK(block_tables.scalar_type() == at::ScalarType::Int &&
+              query_start_loc.scalar_type() == at::ScalarType::Int &&
+              seq_lens.scalar_type() == at::ScalarType::Int);
+  TORCH_CHECK(q.is_contiguous() && out.is_contiguous() &&
+                  k_cache.is_contiguous() && v_cache.is_contiguous() &&
+                  block_tables.is_contiguous() &&
+                  query_start_loc.is_contiguous() && seq_lens.is_contiguous(),
+              "multiq attention takes contiguous tensors");
+  TORCH_CHECK(out.sizes() == q.sizes() && v_cache.sizes() == k_cache.sizes() &&
+              k_cache.size(3) == head_dim && block_tables.size(0) == nseq &&
+              query_start_loc.numel() == nseq + 1);
+  TORCH_CHECK(head_dim == 64 || head_dim == 128, "head_dim 64 or 128");
+  const int group = kvh > 0 ? nheads / kvh : 0;
+  TORCH_CHECK(group >= 1 && group <= 8 && nheads == kvh * group,
+              "nheads must be kvh * group with group <= 8");
+  // two 32-column blocks at head_dim 64, one at head_dim 128
+  TORCH_CHECK(max_query_len >= 1 &&
+                  max_query_len * group <= (head_dim == 64 ? 64 : 32),
+              "max_query_len * group must be at most 64 (head_dim 64) or 32 "
+              "(head_dim 128)");
+  if (nseq == 0 || total_tokens == 0) return;
+
+  const int npart = decode_mfma_num_partitions(nseq, kvh, max_blocks * block_size);
+  auto opts = q.options().dtype(at::ScalarType::Float);
+  const int P = npart * 4;
+  // partials only exist on the partitioned path
+  const long rows = npart > 1 ? total_tokens : 0;
+  auto part_acc = at::empty({rows, nheads, P, head_dim}, opts);
+  auto part_ml = at::empty({rows, nheads, P, 2}, opts);
+  auto* o = reinterpret_cast<__hip_bfloat16*>(out.data_ptr());
+  auto* qp = reinterpret_cast<const __hip_bfloat16*>(q.data_ptr());
+  if (kv_fp8) {
+    launch_paged_multiq_mfma_fp8(
+        o, part_acc.data_ptr<float>(), part_ml.data_ptr<float>(), qp,
+        reinterpret_cast<const unsigned char*>(k_cache.data_ptr()),
+        reinterpret_cast<const unsigned char*>(v_cache.data_ptr()),
+        block_tables.data_ptr<int>(), query_start_loc.data_ptr<int>(),
+        seq_lens.data_ptr<int>(), (float)scale, nseq, total_tokens, nheads,
+        kvh, head_dim, block_size, max_blocks, (int)max_query_len, npart,
+        current_stream());
+    return;
+  }
+  launch_paged_multiq_mfma(
+      o, part_acc.data_ptr<float>(), part_ml.data_ptr<float>(), qp,
+      reinterpret_cast<const __hip_bfloat16*>(k_cache.data_ptr()),
+      reinterpret_cast<const __hip_bfloat16*>(v_cache.data_ptr()),
+      block_tables.data_ptr<int>(), query_start_loc.data_ptr<int>(),
+      seq_lens.data_ptr<int>(), (float)scale, nseq, total_tokens, nheads, kvh,
+      head_dim, block_size, max_blocks, (int)max_query_len, npart,
+      current_stream());
 }
 
 // ---- direct-xGMI all-reduce plumbing (E15) --------------------------------
@@ -707,6 +795,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "paged decode attention (CDNA4)");
   m.def("paged_attention_prefill", &paged_attention_prefill,
         "paged causal prefill attention (CDNA4)");
+  m.def("paged_attention_multiq", &paged_attention_multiq,
+        "paged causal attention for short query chunks, one KV pass per "
+        "(sequence, KV head) (CDNA4 MFMA)");
   m.def("xar_alloc", &xar_alloc,
         "raw hipMalloc + IPC handle for the xGMI all-reduce staging buffer");
   m.def("xar_open", &xar_open, "open a peer's IPC handle -> device pointer");

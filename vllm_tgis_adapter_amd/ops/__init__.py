@@ -158,6 +158,35 @@ def paged_attention_decode(
     return r
 
 
+def paged_attention_multiq_usable(
+    q: torch.Tensor,        # [T, num_heads, head_dim]
+    k_cache: torch.Tensor,  # [num_blocks, block_size, kv_heads, head_dim]
+    max_query_len: int,
+) -> bool:
+    """The short-chunk MFMA attention kernel serves bf16 queries with head_dim
+    64 or 128 over a bf16 or e4m3 (uint8) cache when every sequence's
+    ``q_len * group`` query rows fit its 32-column blocks: GQA group <= 8 and
+    ``max_query_len * group`` <= 64 at head_dim 64 (two blocks), <= 32 at
+    head_dim 128 (one block; two would spill registers there).  That covers
+    speculative verify, prefix-cache hits and short prompts; longer chunks
+    stay on the prefill kernels.  VTA_ATTN_MULTIQ=0 (read per call) turns the
+    route off."""
+    if not (native_enabled(q) and q.dim() == 3 and k_cache.dim() == 4):
+        return False
+    if os.environ.get("VTA_ATTN_MULTIQ", "1") == "0":
+        return False
+    if q.dtype != torch.bfloat16 or k_cache.dtype not in (torch.bfloat16, torch.uint8):
+        return False
+    if not (q.is_contiguous() and k_cache.is_contiguous()):
+        return False
+    nheads, hd, kvh = q.shape[1], q.shape[2], k_cache.shape[2]
+    if hd not in (64, 128) or kvh < 1 or nheads % kvh != 0:
+        return False
+    group = nheads // kvh
+    cols = 64 if hd == 64 else 32
+    return 1 <= group <= 8 and 1 <= max_query_len and max_query_len * group <= cols
+
+
 def paged_attention_prefill(
     q: torch.Tensor,               # [T, num_heads, head_dim]
     k_cache: torch.Tensor,
@@ -171,6 +200,12 @@ def paged_attention_prefill(
 ) -> torch.Tensor:
     if _native(q):
         out = torch.empty_like(q)
+        if paged_attention_multiq_usable(q, k_cache, max_query_len):
+            _C.paged_attention_multiq(
+                out, q, k_cache, v_cache, block_tables, query_start_loc,
+                seq_lens, scale, max_query_len
+            )
+            return out
         _C.paged_attention_prefill(
             out, q, k_cache, v_cache, block_tables, query_start_loc, seq_lens,
             scale, max_query_len
