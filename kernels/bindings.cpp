@@ -112,8 +112,14 @@ void launch_sample_topk_topp(long*, int*, const T*, const float*,
                              hipStream_t);
 int sample_topk_topp_max_vocab();
 void launch_moe_gemm(__hip_bfloat16*, const __hip_bfloat16*,
-                     const __hip_bfloat16*, const int*, int, int, int, int,
-                     bool, hipStream_t);
+                     const __hip_bfloat16*, const int*, const int*, int, int,
+                     int, int, bool, hipStream_t);
+int moe_dispatch_block_tokens();
+template <typename T>
+void launch_moe_dispatch(float*, int*, int*, int*, int*, int*, const T*, int,
+                         int, int, bool, bool, hipStream_t);
+void launch_moe_combine(__hip_bfloat16*, const __hip_bfloat16*, const int*,
+                        const float*, int, int, int, hipStream_t);
 
 namespace {
 
@@ -663,8 +669,110 @@ void moe_gemm(torch::Tensor y, torch::Tensor x, torch::Tensor w,
   launch_moe_gemm(reinterpret_cast<__hip_bfloat16*>(y.data_ptr()),
                   reinterpret_cast<const __hip_bfloat16*>(x.data_ptr()),
                   reinterpret_cast<const __hip_bfloat16*>(w.data_ptr()),
-                  seg_off.data_ptr<int>(), E, N, K, T, gated,
+                  seg_off.data_ptr<int>(), nullptr, E, N, K, T, gated,
                   current_stream());
+}
+
+// moe_gemm on x[src_row] without the copy: y has src_row.numel() rows, x stays
+// in token order.  src_row's values index x's rows; moe_dispatch writes them.
+void moe_gemm_gather(torch::Tensor y, torch::Tensor x, torch::Tensor w,
+                     torch::Tensor seg_off, torch::Tensor src_row,
+                     bool gated) {
+  const int R = src_row.numel();
+  const int K = x.size(1);
+  const int E = w.size(0);
+  const long wn = w.size(1);
+  const int N = gated ? (int)(wn / 2) : (int)wn;
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 3 && y.dim() == 2);
+  TORCH_CHECK(x.scalar_type() == at::ScalarType::BFloat16 &&
+              w.scalar_type() == at::ScalarType::BFloat16 &&
+              y.scalar_type() == at::ScalarType::BFloat16);
+  TORCH_CHECK(seg_off.scalar_type() == at::ScalarType::Int &&
+              seg_off.numel() == E + 1 && seg_off.is_contiguous());
+  TORCH_CHECK(src_row.scalar_type() == at::ScalarType::Int &&
+              src_row.is_contiguous());
+  TORCH_CHECK(N % 128 == 0 && K % 64 == 0 && w.size(2) == K);
+  TORCH_CHECK(y.size(0) == R && y.size(1) == N);
+  TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && y.is_contiguous());
+  if (R == 0) return;
+  TORCH_CHECK(x.size(0) > 0);
+  launch_moe_gemm(reinterpret_cast<__hip_bfloat16*>(y.data_ptr()),
+                  reinterpret_cast<const __hip_bfloat16*>(x.data_ptr()),
+                  reinterpret_cast<const __hip_bfloat16*>(w.data_ptr()),
+                  seg_off.data_ptr<int>(), src_row.data_ptr<int>(), E, N, K,
+                  R, gated, current_stream());
+}
+
+// Route + dispatch.  hist is the [nblk, E] int32 workspace of the two-kernel
+// path (T > moe_dispatch_block_tokens()).  route_only stops after weights and
+// ids; the other outputs may then be empty.
+void moe_dispatch(torch::Tensor logits, torch::Tensor weights,
+                  torch::Tensor ids, torch::Tensor seg_off,
+                  torch::Tensor src_row, torch::Tensor pos,
+                  c10::optional<torch::Tensor> hist, bool route_only) {
+  TORCH_CHECK(logits.dim() == 2 && logits.is_cuda() && logits.is_contiguous());
+  const int Tn = logits.size(0);
+  const int E = logits.size(1);
+  TORCH_CHECK(weights.dim() == 2 && weights.size(0) == Tn);
+  const int k = weights.size(1);
+  const long pairs = (long)Tn * k;
+  TORCH_CHECK(E >= 2 && E <= 64 && k >= 1 && k <= 8 && k <= E);
+  TORCH_CHECK(pairs < (1L << 31));
+  TORCH_CHECK(weights.scalar_type() == at::ScalarType::Float &&
+              weights.is_contiguous());
+  TORCH_CHECK(ids.scalar_type() == at::ScalarType::Int &&
+              ids.is_contiguous() && ids.numel() == pairs);
+  const int nblk =
+      (Tn + moe_dispatch_block_tokens() - 1) / moe_dispatch_block_tokens();
+  int* hp = nullptr;
+  if (!route_only) {
+    for (const torch::Tensor& t : {seg_off, src_row, pos})
+      TORCH_CHECK(t.scalar_type() == at::ScalarType::Int && t.is_contiguous());
+    TORCH_CHECK(seg_off.numel() == E + 1 && src_row.numel() == pairs &&
+                pos.numel() == pairs);
+    if (nblk > 1) {
+      TORCH_CHECK(hist.has_value() &&
+                  hist->scalar_type() == at::ScalarType::Int &&
+                  hist->is_contiguous() && hist->numel() == (long)nblk * E);
+      hp = hist->data_ptr<int>();
+    }
+  }
+  if (Tn == 0) return;
+  const bool vec = E % 8 == 0 &&
+                   reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0;
+  DISPATCH_FLOATING(logits.scalar_type(), {
+    launch_moe_dispatch<scalar_t>(
+        weights.data_ptr<float>(), ids.data_ptr<int>(),
+        route_only ? nullptr : seg_off.data_ptr<int>(),
+        route_only ? nullptr : src_row.data_ptr<int>(),
+        route_only ? nullptr : pos.data_ptr<int>(), hp, cptr<scalar_t>(logits),
+        Tn, E, k, vec, route_only, current_stream());
+  });
+}
+
+void moe_combine(torch::Tensor out, torch::Tensor ye, torch::Tensor pos,
+                 torch::Tensor weights) {
+  TORCH_CHECK(out.dim() == 2 && ye.dim() == 2 && pos.dim() == 2 &&
+              weights.dim() == 2);
+  const int Tn = out.size(0);
+  const int H = out.size(1);
+  const int k = pos.size(1);
+  TORCH_CHECK(out.scalar_type() == at::ScalarType::BFloat16 &&
+              ye.scalar_type() == at::ScalarType::BFloat16 &&
+              pos.scalar_type() == at::ScalarType::Int &&
+              weights.scalar_type() == at::ScalarType::Float);
+  TORCH_CHECK(out.is_contiguous() && ye.is_contiguous() &&
+              pos.is_contiguous() && weights.is_contiguous());
+  TORCH_CHECK(H % 8 == 0 && k >= 1 && k <= 8);
+  TORCH_CHECK(pos.size(0) == Tn && weights.size(0) == Tn &&
+              weights.size(1) == k);
+  TORCH_CHECK(ye.size(0) == (long)Tn * k && ye.size(1) == H);
+  for (const torch::Tensor& t : {out, ye})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0);
+  if (Tn == 0) return;
+  launch_moe_combine(ptr<__hip_bfloat16>(out), cptr<__hip_bfloat16>(ye),
+                     pos.data_ptr<int>(), weights.data_ptr<float>(), Tn, H, k,
+                     current_stream());
 }
 
 void sample_argmax(torch::Tensor out, torch::Tensor logits,
@@ -813,6 +921,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused gate/up skinny GEMM + SiLU-mul, M <= 64 (CDNA4 MFMA)");
   m.def("moe_gemm", &moe_gemm,
         "grouped MoE GEMM over expert segments (CDNA4 MFMA)");
+  m.def("moe_gemm_gather", &moe_gemm_gather,
+        "grouped MoE GEMM that gathers its x rows through src_row");
+  m.def("moe_dispatch", &moe_dispatch,
+        "MoE top-k routing + stable counting-sort dispatch (CDNA4)");
+  m.def("moe_dispatch_block_tokens", &moe_dispatch_block_tokens,
+        "tokens per moe_dispatch workgroup (one launch up to this T)");
+  m.def("moe_combine", &moe_combine,
+        "weighted f32 combine of the experts' sorted output rows (CDNA4)");
   m.def("logsoftmax_topk", &logsoftmax_topk,
         "fused log-softmax + top-K + sampled-token rank (one HBM pass)");
   m.def("sample_argmax", &sample_argmax,

@@ -14,6 +14,11 @@
 // GPU).  Tiling is the 128x128 macro-tile on v_mfma_f32_32x32x16_bf16 with
 // XOR-swizzled LDS chunk staging and the T14 write/load/barrier pipeline,
 // same as gemm_tile_kernel (gemm_skinny.hip).
+//
+// GATHER variant: the activations stay in token order and each staged x row is
+// read from x[src_row[r]] (src_row from moe_dispatch.hip), so the [T*k, K]
+// sorted copy is never written.  Tile, pipeline and epilogue are the same
+// code; the result is bit-identical to the plain kernel on x[src_row].
 
 #include "common.h"
 
@@ -26,12 +31,14 @@ DEVINLINE int mg_swz(int row, int byte_in_row) {
   return row * (MG_KB * 2) + (byte_in_row ^ ((row & 7) << 4));
 }
 
-template <bool GATED>
+template <bool GATED, bool GATHER>
 __global__ __launch_bounds__(256, 2) void moe_gemm_kernel(
     __hip_bfloat16* __restrict__ y,        // [T, N_out] (N_out = I or H)
-    const __hip_bfloat16* __restrict__ x,  // [T, K] sorted by expert
+    const __hip_bfloat16* __restrict__ x,  // [T, K] sorted by expert; GATHER:
+                                           // unsorted, row r is x[src_row[r]]
     const __hip_bfloat16* __restrict__ w,  // [E, (GATED ? 2N : N), K]
     const int* __restrict__ seg_off,       // [E+1] row offsets per expert
+    const int* __restrict__ src_row,       // [T] source row per sorted row
     const int E,
     const int N,   // output width (I for gated, H for plain)
     const int K,
@@ -69,6 +76,14 @@ __global__ __launch_bounds__(256, 2) void moe_gemm_kernel(
             : nullptr;
   const __hip_bfloat16* x_base =
       x + (long)(m_lo + st_row) * K + st_byte / 2;
+  // GATHER: the four staged rows of this thread come from wherever the
+  // dispatch says; the indices are fixed for the whole k loop
+  int x_src[4] = {0, 0, 0, 0};
+  if (GATHER) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      if (p * 32 + st_row < M) x_src[p] = src_row[m_lo + p * 32 + st_row];
+  }
 
   bf16x8_t st_g[4], st_u[4], st_x[4];
   auto stage_load = [&](int chunk) {
@@ -80,7 +95,9 @@ __global__ __launch_bounds__(256, 2) void moe_gemm_kernel(
         st_u[p] = *reinterpret_cast<const bf16x8_t*>(wu_base + (long)(p * 32) * K + koff);
       st_x[p] = bf16x8_t{};
       if (p * 32 + st_row < M)
-        st_x[p] = *reinterpret_cast<const bf16x8_t*>(x_base + (long)(p * 32) * K + koff);
+        st_x[p] = *reinterpret_cast<const bf16x8_t*>(
+            GATHER ? x + (long)x_src[p] * K + st_byte / 2 + koff
+                   : x_base + (long)(p * 32) * K + koff);
     }
   };
   auto stage_write = [&](int buf) {
@@ -166,16 +183,24 @@ __global__ __launch_bounds__(256, 2) void moe_gemm_kernel(
   }
 }
 
+// src_row == nullptr: x is already sorted by expert.  Otherwise T counts the
+// sorted rows (src_row's length) and x is read through src_row.
 void launch_moe_gemm(__hip_bfloat16* y, const __hip_bfloat16* x,
-                     const __hip_bfloat16* w, const int* seg_off, int E,
-                     int N, int K, int T, bool gated, hipStream_t stream) {
+                     const __hip_bfloat16* w, const int* seg_off,
+                     const int* src_row, int E, int N, int K, int T,
+                     bool gated, hipStream_t stream) {
   const int mblk = (T + 127) / 128;
   dim3 grid(N / 128, E * mblk);
   dim3 block(256);
-  if (gated)
-    hipLaunchKernelGGL(moe_gemm_kernel<true>, grid, block, 0, stream, y, x, w,
-                       seg_off, E, N, K, mblk);
-  else
-    hipLaunchKernelGGL(moe_gemm_kernel<false>, grid, block, 0, stream, y, x,
-                       w, seg_off, E, N, K, mblk);
+#define MG_LAUNCH(GATED, GATHER)                                            \
+  hipLaunchKernelGGL((moe_gemm_kernel<GATED, GATHER>), grid, block, 0,      \
+                     stream, y, x, w, seg_off, src_row, E, N, K, mblk)
+  if (src_row) {
+    if (gated) MG_LAUNCH(true, true);
+    else MG_LAUNCH(false, true);
+  } else {
+    if (gated) MG_LAUNCH(true, false);
+    else MG_LAUNCH(false, false);
+  }
+#undef MG_LAUNCH
 }

@@ -9,9 +9,15 @@ through the grouped-GEMM HIP kernel (kernels/moe_gemm.hip): tokens sorted by
 expert, one fused gate/up+SiLU launch plus one down launch covering every
 expert segment — shape-static, so MoE decode steps hipGraph-capture; a
 per-expert torch loop remains as the fallback for non-128-aligned dims.
+Routing, the sort bookkeeping, the activation gather and the weighted combine
+around those two launches are HIP as well (kernels/moe_dispatch.hip), which
+makes the TP-sharded block four launches after the router GEMM (five above
+256 tokens, where the dispatch takes two).
 """
 
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn as nn
@@ -105,6 +111,19 @@ class MoEBlock(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:  # [T, H]
         t = x.shape[0]
         router_logits = F.linear(x, self.gate)           # [T, E]
+        if (not self.ep and t > 0
+                and os.environ.get("VTA_MOE_FUSED", "1") != "0"
+                and ops.moe_gemm_usable(x, self.hidden, self.inter)
+                and ops.moe_dispatch_usable(router_logits, self.top_k)):
+            # fused chain (E16): route + dispatch, a gated grouped GEMM that
+            # gathers its own rows, the down grouped GEMM, an f32 combine.
+            # Launch only, shapes depend on T alone, so it still captures.
+            # VTA_MOE_FUSED=0 (read per call) keeps the torch chain below.
+            weights, _, seg, src_row, pos = ops.moe_dispatch(
+                router_logits, self.top_k)
+            h = ops.moe_gemm(x, self.w13, seg, gated=True, rows=src_row)
+            ye = ops.moe_gemm(h, self.w2, seg, gated=False)
+            return tp_all_reduce(ops.moe_combine(ye, pos, weights))
         weights, ids = ops.topk_softmax(router_logits, self.top_k)  # [T, k]
         out = torch.zeros_like(x)
         flat_ids = ids.reshape(-1)                        # [T*k]

@@ -488,10 +488,17 @@ def moe_gemm(
     w: torch.Tensor,        # [E, 2N, K] (gated) or [E, N, K]
     seg_off: torch.Tensor,  # [E+1] int32 device row offsets
     gated: bool,
+    rows: torch.Tensor | None = None,  # [R] int32: sorted row r is x[rows[r]]
 ) -> torch.Tensor:
-    """Grouped GEMM over expert segments (E16); gated fuses SiLU(g)*u."""
+    """Grouped GEMM over expert segments (E16); gated fuses SiLU(g)*u.  With
+    ``rows`` (moe_dispatch's src_row) x stays in token order and the kernel
+    gathers its rows itself: same bits as on ``x[rows].contiguous()``."""
     assert _native(x)
     n = w.shape[1] // 2 if gated else w.shape[1]
+    if rows is not None:
+        out = torch.empty((rows.numel(), n), dtype=x.dtype, device=x.device)
+        _C.moe_gemm_gather(out, x, w, seg_off, rows, gated)
+        return out
     out = torch.empty((x.shape[0], n), dtype=x.dtype, device=x.device)
     _C.moe_gemm(out, x, w, seg_off, gated)
     return out
@@ -507,8 +514,80 @@ def moe_gemm_usable(x: torch.Tensor, hidden: int, inter: int) -> bool:
     )
 
 
+def moe_dispatch_usable(router_logits: torch.Tensor, top_k: int) -> bool:
+    """The route + dispatch kernels serve contiguous [T, E] bf16 / f16 / f32
+    logits with 2 <= E <= 64 and 1 <= top_k <= min(E, 8)."""
+    return (native_enabled(router_logits) and router_logits.dim() == 2
+            and router_logits.dtype in (torch.bfloat16, torch.float16, torch.float32)
+            and router_logits.is_contiguous()
+            and 2 <= router_logits.shape[1] <= 64
+            and 1 <= top_k <= min(router_logits.shape[1], 8)
+            and router_logits.shape[0] * top_k < 2 ** 31)
+
+
+def moe_dispatch_block_tokens() -> int:
+    """Tokens per moe_dispatch workgroup: up to this T the op is one launch,
+    above it two."""
+    return _C.moe_dispatch_block_tokens()
+
+
+def moe_dispatch(router_logits: torch.Tensor, top_k: int):
+    """MoE routing and dispatch (E16) -> (weights f32 [T,k], ids i32 [T,k],
+    seg_off i32 [E+1], src_row i32 [T*k], pos i32 [T,k]).
+
+    Top-k on the logits by descending value (ties to the lower expert),
+    softmax over the selected logits, and a stable counting sort of the
+    (token, slot) pairs by expert, token, slot: ``seg_off`` is moe_gemm's
+    segment array, ``src_row`` its ``rows``, ``pos`` what moe_combine reads.
+    Launch only, no host sync; repeats bit for bit."""
+    if not _native(router_logits):
+        return reference.moe_dispatch(router_logits, top_k)
+    assert moe_dispatch_usable(router_logits, top_k), \
+        "moe_dispatch needs moe_dispatch_usable()"
+    t, e = router_logits.shape
+    dev = router_logits.device
+    weights = torch.empty((t, top_k), dtype=torch.float32, device=dev)
+    ids = torch.empty((t, top_k), dtype=torch.int32, device=dev)
+    src_row = torch.empty((t * top_k,), dtype=torch.int32, device=dev)
+    pos = torch.empty((t, top_k), dtype=torch.int32, device=dev)
+    if t == 0:
+        return (weights, ids, torch.zeros(e + 1, dtype=torch.int32, device=dev),
+                src_row, pos)
+    seg_off = torch.empty((e + 1,), dtype=torch.int32, device=dev)
+    blk = _C.moe_dispatch_block_tokens()
+    hist = None
+    if t > blk:
+        hist = torch.empty(((t + blk - 1) // blk, e), dtype=torch.int32, device=dev)
+    _C.moe_dispatch(router_logits, weights, ids, seg_off, src_row, pos, hist, False)
+    return weights, ids, seg_off, src_row, pos
+
+
+def moe_combine(
+    ye: torch.Tensor,       # [T*k, H] expert outputs in sorted order
+    pos: torch.Tensor,      # [T, k] int32 sorted position of each pair
+    weights: torch.Tensor,  # [T, k] float32
+) -> torch.Tensor:
+    """out[t] = sum_j weights[t, j] * ye[pos[t, j]]: f32 accumulation in slot
+    order, rounded once (E16)."""
+    if not _native(ye):
+        return reference.moe_combine(ye, pos, weights)
+    out = torch.empty((pos.shape[0], ye.shape[1]), dtype=ye.dtype, device=ye.device)
+    _C.moe_combine(out, ye, pos, weights)
+    return out
+
+
 def topk_softmax(gate_logits: torch.Tensor, top_k: int):
-    # Router math is tiny; torch ops are fine on both devices for now.
+    """MoE router -> (f32 weights [T,k], int64 ids [T,k]).  GPU logits inside
+    moe_dispatch_usable() run the route stage of moe_dispatch; everything
+    else is the torch reference."""
+    if gate_logits.shape[0] > 0 and moe_dispatch_usable(gate_logits, top_k):
+        t = gate_logits.shape[0]
+        dev = gate_logits.device
+        weights = torch.empty((t, top_k), dtype=torch.float32, device=dev)
+        ids = torch.empty((t, top_k), dtype=torch.int32, device=dev)
+        none = torch.empty((0,), dtype=torch.int32, device=dev)
+        _C.moe_dispatch(gate_logits, weights, ids, none, none, none, None, True)
+        return weights, ids.long()
     return reference.topk_softmax(gate_logits, top_k)
 
 

@@ -148,3 +148,31 @@ def topk_softmax(gate_logits: torch.Tensor, top_k: int) -> tuple[torch.Tensor, t
     weights, ids = torch.topk(probs, top_k, dim=-1)
     weights = weights / weights.sum(dim=-1, keepdim=True)
     return weights, ids
+
+
+def moe_dispatch(gate_logits: torch.Tensor, top_k: int):
+    """MoE routing plus the sorted-by-expert bookkeeping of the grouped GEMM.
+
+    Top-k on the logits (ties to the lower expert), softmax over the selected
+    logits, then a stable sort of the (token, slot) pairs by expert.  Returns
+    (weights f32 [T,k], ids i32 [T,k], seg_off i32 [E+1], src_row i32 [T*k],
+    pos i32 [T,k])."""
+    t, e = gate_logits.shape
+    vals, ids = torch.sort(gate_logits.float(), dim=-1, descending=True, stable=True)
+    vals, ids = vals[:, :top_k], ids[:, :top_k]
+    weights = torch.softmax(vals, dim=-1)
+    flat = ids.reshape(-1)
+    order = torch.argsort(flat, stable=True)
+    seg_off = torch.zeros(e + 1, dtype=torch.int32, device=flat.device)
+    seg_off[1:] = torch.bincount(flat, minlength=e).cumsum(0)
+    src_row = (order // top_k).to(torch.int32)
+    pos = torch.empty_like(order)
+    pos[order] = torch.arange(order.numel(), device=order.device)
+    return (weights, ids.to(torch.int32), seg_off, src_row,
+            pos.to(torch.int32).reshape(t, top_k))
+
+
+def moe_combine(ye: torch.Tensor, pos: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+    """out[t] = sum_j weights[t, j] * ye[pos[t, j]], f32 sum rounded once."""
+    rows = ye[pos.long()].float()                    # [T, k, H]
+    return (rows * weights.float()[..., None]).sum(dim=1).to(ye.dtype)
