@@ -69,6 +69,12 @@ void launch_reshape_and_cache_fp8(const __hip_bfloat16*,
 void launch_gemm_skinny_q(__hip_bfloat16*, float*, const __hip_bfloat16*,
                           const unsigned char*, const float*, int, int, int,
                           int, int, hipStream_t);
+int gemm_tile_q_num_ksplit(int M, int N, int K);
+void launch_gemm_tile_q(__hip_bfloat16*, float*, const __hip_bfloat16*,
+                        const unsigned char*, const float*, int, int, int,
+                        int, int, hipStream_t);
+void launch_dequant_weight(__hip_bfloat16*, const unsigned char*,
+                           const float*, int, int, int, hipStream_t);
 void launch_gemm_skinny(__hip_bfloat16*, float*, const __hip_bfloat16*,
                         const __hip_bfloat16*, int, int, int, int,
                         hipStream_t);
@@ -550,6 +556,72 @@ void gemm_skinny_q(torch::Tensor y, torch::Tensor x, torch::Tensor wq,
       wscale.data_ptr<float>(), (int)qbits, M, N, K, KS, current_stream());
 }
 
+static void check_quant_storage(const torch::Tensor& wq,
+                                const torch::Tensor& wscale, int64_t qbits,
+                                int N, int K) {
+  TORCH_CHECK(qbits == 8 || qbits == 4);
+  TORCH_CHECK(wq.scalar_type() == at::ScalarType::Byte ||
+              wq.scalar_type() == at::ScalarType::Char);
+  TORCH_CHECK(wscale.scalar_type() == at::ScalarType::Float);
+  TORCH_CHECK(wq.is_cuda() && wscale.is_cuda());
+  TORCH_CHECK(wq.is_contiguous() && wscale.is_contiguous());
+  TORCH_CHECK(N >= 128 && N % 128 == 0 && K >= 128 && K % 128 == 0);
+  TORCH_CHECK(wq.dim() == 2 && wq.size(1) == (qbits == 8 ? K : K / 2));
+  TORCH_CHECK(wscale.numel() == (qbits == 8 ? (int64_t)N
+                                            : (int64_t)N * (K / 128)));
+  // the kernels fetch the packed bytes as 16-byte vectors
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0);
+}
+
+int64_t gemm_tile_q_ksplit(int64_t M, int64_t N, int64_t K) {
+  return gemm_tile_q_num_ksplit((int)M, (int)N, (int)K);
+}
+
+void gemm_tile_q(torch::Tensor y, torch::Tensor x, torch::Tensor wq,
+                 torch::Tensor wscale, int64_t qbits) {
+  TORCH_CHECK(x.dim() == 2 && y.dim() == 2);
+  const int M = x.size(0);
+  const int K = x.size(1);
+  const int N = wq.size(0);
+  TORCH_CHECK(x.scalar_type() == at::ScalarType::BFloat16 &&
+              y.scalar_type() == at::ScalarType::BFloat16);
+  TORCH_CHECK(x.is_cuda() && y.is_cuda());
+  TORCH_CHECK(x.is_contiguous() && y.is_contiguous());
+  TORCH_CHECK(M >= 1);
+  check_quant_storage(wq, wscale, qbits, N, K);
+  TORCH_CHECK(y.size(0) == M && y.size(1) == N);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(y.data_ptr()) % 8 == 0);
+  const int KS = gemm_tile_q_num_ksplit(M, N, K);
+  torch::Tensor part;
+  float* pp = nullptr;
+  if (KS > 1) {
+    part = at::empty({KS, M, N}, x.options().dtype(at::ScalarType::Float));
+    pp = part.data_ptr<float>();
+  }
+  launch_gemm_tile_q(
+      reinterpret_cast<__hip_bfloat16*>(y.data_ptr()), pp,
+      reinterpret_cast<const __hip_bfloat16*>(x.data_ptr()),
+      reinterpret_cast<const unsigned char*>(wq.data_ptr()),
+      wscale.data_ptr<float>(), (int)qbits, M, N, K, KS, current_stream());
+}
+
+void dequant_weight(torch::Tensor out, torch::Tensor wq, torch::Tensor wscale,
+                    int64_t qbits) {
+  TORCH_CHECK(out.dim() == 2);
+  const int N = out.size(0);
+  const int K = out.size(1);
+  TORCH_CHECK(out.scalar_type() == at::ScalarType::BFloat16);
+  TORCH_CHECK(out.is_cuda() && out.is_contiguous());
+  TORCH_CHECK(wq.size(0) == N);
+  check_quant_storage(wq, wscale, qbits, N, K);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0);
+  launch_dequant_weight(
+      reinterpret_cast<__hip_bfloat16*>(out.data_ptr()),
+      reinterpret_cast<const unsigned char*>(wq.data_ptr()),
+      wscale.data_ptr<float>(), (int)qbits, N, K, current_stream());
+}
+
 void gemm_skinny_gated(torch::Tensor y, torch::Tensor x, torch::Tensor w13) {
   const int M = x.size(0);
   const int K = x.size(1);
@@ -915,6 +987,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "128x128-tile glds-staged bf16 GEMM for decode batches (CDNA4)");
   m.def("gemm_skinny_q", &gemm_skinny_q,
         "weight-only-quantized (int8 / int4-g128) skinny decode GEMM");
+  m.def("gemm_tile_q", &gemm_tile_q,
+        "weight-only-quantized (int8 / int4-g128) tile GEMM, M > 64");
+  m.def("gemm_tile_q_ksplit", &gemm_tile_q_ksplit,
+        "K-split count gemm_tile_q uses for (M, N, K)");
+  m.def("dequant_weight", &dequant_weight,
+        "one-pass int8 / int4-g128 -> bf16 weight dequantisation");
   m.def("gemm_skinny", &gemm_skinny,
         "skinny decode GEMM y = x @ w^T, M <= 64 (CDNA4 MFMA)");
   m.def("gemm_skinny_gated", &gemm_skinny_gated,

@@ -294,9 +294,26 @@ def quantize_weight(w: torch.Tensor, qbits: int) -> tuple[torch.Tensor, torch.Te
 
 def dequantize_weight(wq: torch.Tensor, scales: torch.Tensor, qbits: int,
                       dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """bf16 on a GPU runs the one-pass HIP kernel (bit-identical to the torch
+    chain below, which serves CPU tensors, other dtypes and
+    VTA_FORCE_REFERENCE=1; VTA_QDEQUANT_NATIVE=0 forces the chain for
+    comparison)."""
+    n = wq.shape[0]
+    k = wq.shape[1] * (8 // qbits)
+    if (
+        dtype == torch.bfloat16
+        and _native(wq)
+        and n % 128 == 0
+        and k % 128 == 0
+        and wq.is_contiguous()
+        and scales.is_contiguous()
+        and os.environ.get("VTA_QDEQUANT_NATIVE", "1") != "0"
+    ):
+        out = torch.empty((n, k), dtype=dtype, device=wq.device)
+        _C.dequant_weight(out, wq, scales, qbits)
+        return out
     if qbits == 8:
         return (wq.float() * scales.unsqueeze(1)).to(dtype)
-    n = wq.shape[0]
     lo = (wq & 0xF).to(torch.float32) - 8.0
     hi = (wq >> 4).to(torch.float32) - 8.0
     q = torch.stack([lo, hi], dim=2).view(n, -1)  # interleave even/odd k
@@ -304,11 +321,24 @@ def dequantize_weight(wq: torch.Tensor, scales: torch.Tensor, qbits: int,
     return (q.view(n, k // 128, 128) * scales.unsqueeze(2)).view(n, k).to(dtype)
 
 
+# largest M served by gemm_tile_q, per qbits: the largest measured M at which
+# it beats one-pass dequant + hipBLASLt on all four llama-3-8b linears
+_QGEMM_TILE_MAX_M = {8: 256, 4: 256}
+
+
 def linear_quant(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor,
                  qbits: int, bias: torch.Tensor | None = None) -> torch.Tensor:
-    """W8A16/W4A16 linear: native dequant-GEMM for decode batches, dequant +
-    hipBLASLt above (prefill is compute-bound; the quant win is the weight
-    stream at small M)."""
+    """W8A16/W4A16 linear, native at every batch size.
+
+    M <= 64 runs the skinny dequant-GEMM (weight-stream bound).  Above that,
+    up to the cutover, the dequant-in-LDS tile GEMM (gemm_tile_q.hip) reads
+    the packed weights directly; past the cutover, where the conversion work
+    no longer hides under the MFMAs, the weight is dequantised in one HIP
+    pass and handed to hipBLASLt.  A bias or a shape the kernels reject
+    (N or K not a multiple of 128) also takes the dequant + F.linear path.
+    All three see bit-identical effective weights.  The cutover defaults to
+    _QGEMM_TILE_MAX_M[qbits] (measured, profiles/r08_gemm_tile_q.txt);
+    VTA_QGEMM_TILE_MAX_M overrides it and 0 disables the tile kernel."""
     x2 = x.reshape(-1, x.shape[-1])
     m = x2.shape[0]
     n = wq.shape[0]
@@ -317,14 +347,20 @@ def linear_quant(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor,
         bias is None
         and _native(x)
         and x.dtype == torch.bfloat16
-        and 1 <= m <= 64
+        and m >= 1
         and n % 128 == 0
         and k % 128 == 0
         and x2.is_contiguous()
     ):
-        out = torch.empty((m, n), dtype=x.dtype, device=x.device)
-        _C.gemm_skinny_q(out, x2, wq, scales, qbits)
-        return out.view(*x.shape[:-1], n)
+        tile_max_m = int(os.environ.get("VTA_QGEMM_TILE_MAX_M",
+                                        _QGEMM_TILE_MAX_M[qbits]))
+        if m <= 64 or m <= tile_max_m:
+            out = torch.empty((m, n), dtype=x.dtype, device=x.device)
+            if m <= 64:
+                _C.gemm_skinny_q(out, x2, wq, scales, qbits)
+            else:
+                _C.gemm_tile_q(out, x2, wq, scales, qbits)
+            return out.view(*x.shape[:-1], n)
     w = dequantize_weight(wq, scales, qbits, x.dtype)
     return torch.nn.functional.linear(x, w, bias)
 
