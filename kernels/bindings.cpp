@@ -120,6 +120,11 @@ int sample_topk_topp_max_vocab();
 void launch_moe_gemm(__hip_bfloat16*, const __hip_bfloat16*,
                      const __hip_bfloat16*, const int*, const int*, int, int,
                      int, int, bool, hipStream_t);
+int moe_gemm_q_block_m(int R, int E);
+void launch_moe_gemm_q(__hip_bfloat16*, const __hip_bfloat16*,
+                       const unsigned char*, const float*, const int*,
+                       const int*, int, int, int, int, int, bool,
+                       hipStream_t);
 int moe_dispatch_block_tokens();
 template <typename T>
 void launch_moe_dispatch(float*, int*, int*, int*, int*, int*, const T*, int,
@@ -775,6 +780,64 @@ void moe_gemm_gather(torch::Tensor y, torch::Tensor x, torch::Tensor w,
                   R, gated, current_stream());
 }
 
+// moe_gemm / moe_gemm_gather on quantized expert stacks: wq [E, rows, K] int8
+// with scales [E, rows], or wq [E, rows, K/2] uint8 nibbles with scales
+// [E, rows, K/128].  With src_row, y has src_row.numel() rows and x stays in
+// token order.
+int64_t moe_gemm_q_tile_rows(int64_t R, int64_t E) {
+  return moe_gemm_q_block_m((int)R, (int)E);
+}
+
+void moe_gemm_q(torch::Tensor y, torch::Tensor x, torch::Tensor wq,
+                torch::Tensor wscale, torch::Tensor seg_off,
+                c10::optional<torch::Tensor> src_row, bool gated,
+                int64_t qbits) {
+  TORCH_CHECK(x.dim() == 2 && wq.dim() == 3 && y.dim() == 2);
+  TORCH_CHECK(qbits == 8 || qbits == 4);
+  const int R = src_row ? (int)src_row->numel() : (int)x.size(0);
+  const int K = x.size(1);
+  const int E = wq.size(0);
+  const long wn = wq.size(1);
+  const int N = gated ? (int)(wn / 2) : (int)wn;
+  TORCH_CHECK(x.scalar_type() == at::ScalarType::BFloat16 &&
+              y.scalar_type() == at::ScalarType::BFloat16);
+  TORCH_CHECK(wq.scalar_type() ==
+              (qbits == 8 ? at::ScalarType::Char : at::ScalarType::Byte));
+  TORCH_CHECK(wscale.scalar_type() == at::ScalarType::Float);
+  TORCH_CHECK(seg_off.scalar_type() == at::ScalarType::Int &&
+              seg_off.numel() == E + 1 && seg_off.is_contiguous());
+  TORCH_CHECK(E >= 1 && N >= 128 && N % 128 == 0 && (!gated || wn == 2L * N));
+  TORCH_CHECK(K >= 64 && K % 64 == 0 && (qbits == 8 || K % 128 == 0));
+  TORCH_CHECK(wq.size(2) == (qbits == 8 ? K : K / 2));
+  TORCH_CHECK(wscale.dim() == (qbits == 8 ? 2 : 3) && wscale.size(0) == E &&
+              wscale.size(1) == wn &&
+              (qbits == 8 || wscale.size(2) == K / 128));
+  TORCH_CHECK(y.size(0) == R && y.size(1) == N);
+  TORCH_CHECK(x.is_cuda() && y.is_cuda() && wq.is_cuda() &&
+              wscale.is_cuda() && seg_off.is_cuda());
+  TORCH_CHECK(x.is_contiguous() && wq.is_contiguous() &&
+              wscale.is_contiguous() && y.is_contiguous());
+  // 16-byte x / packed-weight vectors, 8-byte y stores
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(y.data_ptr()) % 8 == 0);
+  const int* rows = nullptr;
+  if (src_row) {
+    TORCH_CHECK(src_row->scalar_type() == at::ScalarType::Int &&
+                src_row->is_contiguous() && src_row->is_cuda());
+    rows = src_row->data_ptr<int>();
+  }
+  if (R == 0) return;
+  TORCH_CHECK(x.size(0) > 0);
+  const int bm = moe_gemm_q_block_m(R, E);
+  TORCH_CHECK((long)E * ((R + bm - 1) / bm) <= 65535);
+  launch_moe_gemm_q(reinterpret_cast<__hip_bfloat16*>(y.data_ptr()),
+                    reinterpret_cast<const __hip_bfloat16*>(x.data_ptr()),
+                    reinterpret_cast<const unsigned char*>(wq.data_ptr()),
+                    wscale.data_ptr<float>(), seg_off.data_ptr<int>(), rows,
+                    (int)qbits, E, N, K, R, gated, current_stream());
+}
+
 // Route + dispatch.  hist is the [nblk, E] int32 workspace of the two-kernel
 // path (T > moe_dispatch_block_tokens()).  route_only stops after weights and
 // ids; the other outputs may then be empty.
@@ -1001,6 +1064,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grouped MoE GEMM over expert segments (CDNA4 MFMA)");
   m.def("moe_gemm_gather", &moe_gemm_gather,
         "grouped MoE GEMM that gathers its x rows through src_row");
+  m.def("moe_gemm_q", &moe_gemm_q,
+        "grouped MoE GEMM on int8 / int4-g128 expert weights (CDNA4 MFMA)");
+  m.def("moe_gemm_q_tile_rows", &moe_gemm_q_tile_rows,
+        "x rows per workgroup moe_gemm_q uses for (R, E)");
   m.def("moe_dispatch", &moe_dispatch,
         "MoE top-k routing + stable counting-sort dispatch (CDNA4)");
   m.def("moe_dispatch_block_tokens", &moe_dispatch_block_tokens,

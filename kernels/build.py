@@ -25,8 +25,9 @@ def build(verbose: bool = True, force: bool = False) -> Path:
     import torch.utils.cpp_extension as ce
 
     sources = sorted(KERNELS.glob("*.hip")) + [KERNELS / "bindings.cpp"]
+    headers = sorted(KERNELS.glob("*.h"))
     if OUT.exists() and not force:
-        newest_src = max(p.stat().st_mtime for p in sources + [KERNELS / "common.h"])
+        newest_src = max(p.stat().st_mtime for p in sources + headers)
         if OUT.stat().st_mtime > newest_src:
             if verbose:
                 print(f"[kernels/build] {OUT} up to date")
@@ -60,7 +61,7 @@ def build(verbose: bool = True, force: bool = False) -> Path:
         obj = build_dir / (src.stem + ".o")
         objects.append(obj)
         if obj.exists() and not force and obj.stat().st_mtime > max(
-            src.stat().st_mtime, (KERNELS / "common.h").stat().st_mtime
+            p.stat().st_mtime for p in [src] + headers
         ):
             continue
         cmd = ["hipcc", "-c", str(src), "-o", str(obj)] + common_flags

@@ -218,14 +218,17 @@ class Worker:
 
     # ------------------------------------------------------------------
     def _quantize_model(self, method: str) -> None:
-        """Weight-only RTN quantization of the attention/MLP linears (E18).
+        """Weight-only RTN quantization of the attention/MLP linears and the
+        MoE expert weights (E18).
 
         --quantize int8 -> per-channel int8; int4 / awq / gptq / squeezellm
         -> packed int4 with group-128 scales (the 4-bit storage profile of
         those methods; checkpoint-specific scales are not available offline,
         so RTN is applied to the loaded weights).  Embedding / lm_head stay
-        bf16 (their accuracy sensitivity; standard practice).
+        bf16 (their accuracy sensitivity; standard practice), as does the MoE
+        router gate.
         """
+        from ..models.mixtral import MoEBlock
         from ..parallel.layers import (
             ColumnParallelLinear,
             MergedColumnParallelLinear,
@@ -236,7 +239,7 @@ class Worker:
         qbits = 8 if method == "int8" else 4
         kinds = (ColumnParallelLinear, MergedColumnParallelLinear,
                  RowParallelLinear)
-        count = 0
+        count = moe_count = 0
         for mod in self.model.modules():
             if isinstance(mod, kinds) and hasattr(mod, "weight"):
                 # int4 scales group along K (128); int8 has no shape need —
@@ -246,9 +249,11 @@ class Worker:
                     continue
                 quantize_module_(mod, qbits)
                 count += 1
+            elif isinstance(mod, MoEBlock) and mod.quantize_(qbits):
+                moe_count += 1
         if self.device == "cuda":
             torch.cuda.empty_cache()
-        print(f"[worker] quantized {count} linears to "
+        print(f"[worker] quantized {count} linears and {moe_count} MoE blocks to "
               f"{'int8' if qbits == 8 else 'int4-g128'} ({method})", flush=True)
 
     def add_lora(self, lora_path: str, lora_int_id: int) -> None:

@@ -56,6 +56,41 @@ class MoEBlock(nn.Module):
         # w13: [E_local, 2*I_local, H] fused gate+up; w2: [E_local, H, I_local]
         self.w13 = _init_weight((n_local, 2 * self.inter, cfg.hidden_size), cfg.dtype)
         self.w2 = _init_weight((n_local, cfg.hidden_size, self.inter), cfg.dtype)
+        self.quant_bits: int | None = None  # set by quantize_()
+
+    def quantize_(self, qbits: int) -> bool:
+        """Replace the bf16 expert weights with RTN-quantized storage (E18):
+        buffers w13_q / w13_scale / w2_q / w2_scale in ops.quantize_weight's
+        format stacked per expert.  int4 groups scales over 128 k, so a block
+        whose hidden or local intermediate size is no multiple of 128 stays
+        bf16 (returns False).  The router gate stays bf16."""
+        if qbits == 4 and (self.hidden % 128 or self.inter % 128):
+            return False
+        for name in ("w13", "w2"):
+            w = getattr(self, name).data
+            # one expert at a time: the f32 working set stays one expert wide
+            packed = [ops.quantize_weight(w[e], qbits) for e in range(w.shape[0])]
+            delattr(self, name)
+            self.register_buffer(name + "_q", torch.stack([q for q, _ in packed]))
+            self.register_buffer(name + "_scale", torch.stack([s for _, s in packed]))
+        self.quant_bits = qbits
+        return True
+
+    def _grouped(self, x, name: str, seg, gated: bool, rows=None):
+        """ops.moe_gemm on w13 / w2, packed or bf16."""
+        if self.quant_bits is None:
+            return ops.moe_gemm(x, getattr(self, name), seg, gated=gated, rows=rows)
+        return ops.moe_gemm(x, getattr(self, name + "_q"), seg, gated=gated,
+                            rows=rows, scales=getattr(self, name + "_scale"),
+                            qbits=self.quant_bits)
+
+    def _expert(self, name: str, e: int, dtype: torch.dtype) -> torch.Tensor:
+        """One expert's w13 / w2 for the per-expert loops, dequantised on use."""
+        if self.quant_bits is None:
+            return getattr(self, name)[e]
+        return ops.dequantize_weight(getattr(self, name + "_q")[e],
+                                     getattr(self, name + "_scale")[e],
+                                     self.quant_bits, dtype)
 
     def _forward_ep(self, x: torch.Tensor, flat_ids, flat_w, token_idx):
         """Dispatch token copies to their experts' owner ranks (all-to-all),
@@ -89,15 +124,16 @@ class MoEBlock(nn.Module):
                 0, local_e, torch.ones_like(local_e, dtype=torch.int32))
             seg = torch.zeros(epr + 1, dtype=torch.int32, device=x.device)
             seg[1:] = counts.cumsum(0).to(torch.int32)
-            h = ops.moe_gemm(xs, self.w13, seg, gated=True)
-            ye_sorted = ops.moe_gemm(h, self.w2, seg, gated=False)
+            h = self._grouped(xs, "w13", seg, gated=True)
+            ye_sorted = self._grouped(h, "w2", seg, gated=False)
         else:
             ye_sorted = torch.empty_like(xs)
             sorted_e = local_e[order2]
             for e in range(epr):
                 sel = (sorted_e == e).nonzero(as_tuple=True)[0]
-                h = ops.silu_and_mul(F.linear(xs[sel], self.w13[e]))
-                ye_sorted[sel] = F.linear(h, self.w2[e])
+                h = ops.silu_and_mul(
+                    F.linear(xs[sel], self._expert("w13", e, x.dtype)))
+                ye_sorted[sel] = F.linear(h, self._expert("w2", e, x.dtype))
         ye = torch.empty_like(ye_sorted)
         ye[order2] = ye_sorted
 
@@ -121,8 +157,8 @@ class MoEBlock(nn.Module):
             # VTA_MOE_FUSED=0 (read per call) keeps the torch chain below.
             weights, _, seg, src_row, pos = ops.moe_dispatch(
                 router_logits, self.top_k)
-            h = ops.moe_gemm(x, self.w13, seg, gated=True, rows=src_row)
-            ye = ops.moe_gemm(h, self.w2, seg, gated=False)
+            h = self._grouped(x, "w13", seg, gated=True, rows=src_row)
+            ye = self._grouped(h, "w2", seg, gated=False)
             return tp_all_reduce(ops.moe_combine(ye, pos, weights))
         weights, ids = ops.topk_softmax(router_logits, self.top_k)  # [T, k]
         out = torch.zeros_like(x)
@@ -143,8 +179,8 @@ class MoEBlock(nn.Module):
             seg = torch.zeros(self.num_experts + 1, dtype=torch.int32, device=x.device)
             seg[1:] = counts.cumsum(0).to(torch.int32)
             xs = x[rows].contiguous()
-            h = ops.moe_gemm(xs, self.w13, seg, gated=True)
-            ye = ops.moe_gemm(h, self.w2, seg, gated=False)
+            h = self._grouped(xs, "w13", seg, gated=True)
+            ye = self._grouped(h, "w2", seg, gated=False)
             out.index_add_(0, rows, ye * flat_w[sort_idx, None])
             return tp_all_reduce(out)
         # Launch-only expert loop: no data-dependent host branches (`any()`
@@ -154,8 +190,8 @@ class MoEBlock(nn.Module):
             sel = (flat_ids == e).nonzero(as_tuple=True)[0]
             rows = token_idx[sel]
             xe = x[rows]
-            h = ops.silu_and_mul(F.linear(xe, self.w13[e]))
-            ye = F.linear(h, self.w2[e])
+            h = ops.silu_and_mul(F.linear(xe, self._expert("w13", e, x.dtype)))
+            ye = F.linear(h, self._expert("w2", e, x.dtype))
             out.index_add_(0, rows, ye * flat_w[sel, None])
         return tp_all_reduce(out)
 

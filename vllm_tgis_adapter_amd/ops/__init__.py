@@ -519,24 +519,52 @@ def logsoftmax_topk(
     return topv, topi, chosen_lp, ranks
 
 
+# largest sorted-row count served by the fused quantized grouped GEMM, per
+# qbits: the largest measured R at which its slowest round beats one-pass
+# dequant + bf16 moe_gemm's fastest on both the gated and the down GEMM, at
+# mixtral-8x7b's TP=1 and TP=4 dims (profiles/r09_moe_gemm_q.txt)
+_MOE_QGEMM_MAX_ROWS = {8: 4096, 4: 4096}
+
+
 def moe_gemm(
     x: torch.Tensor,        # [T, K] rows sorted by expert
     w: torch.Tensor,        # [E, 2N, K] (gated) or [E, N, K]
     seg_off: torch.Tensor,  # [E+1] int32 device row offsets
     gated: bool,
     rows: torch.Tensor | None = None,  # [R] int32: sorted row r is x[rows[r]]
+    scales: torch.Tensor | None = None,
+    qbits: int | None = None,
 ) -> torch.Tensor:
     """Grouped GEMM over expert segments (E16); gated fuses SiLU(g)*u.  With
     ``rows`` (moe_dispatch's src_row) x stays in token order and the kernel
-    gathers its rows itself: same bits as on ``x[rows].contiguous()``."""
+    gathers its rows itself: same bits as on ``x[rows].contiguous()``.
+
+    With ``scales`` and ``qbits`` (8 | 4), ``w`` is quantize_weight's storage
+    stacked per expert: int8 [E, rows, K] with scales [E, rows], or uint8
+    nibbles [E, rows, K/2] with scales [E, rows, K/128].  Up to the cutover in
+    sorted rows the dequant-in-LDS kernel (moe_gemm_q.hip) reads the packed
+    weights directly; past it, where the conversion work no longer hides
+    under the MFMAs, the flattened stack is dequantised in one HIP pass into a
+    transient bf16 tensor for the bf16 kernel.  Both see bit-identical
+    weights.  The cutover defaults to _MOE_QGEMM_MAX_ROWS[qbits];
+    VTA_MOE_QGEMM_MAX_ROWS overrides it and 0 disables the fused kernel."""
     assert _native(x)
+    assert (scales is None) == (qbits is None)
     n = w.shape[1] // 2 if gated else w.shape[1]
+    r = rows.numel() if rows is not None else x.shape[0]
+    out = torch.empty((r, n), dtype=x.dtype, device=x.device)
+    if scales is not None:
+        max_rows = int(os.environ.get("VTA_MOE_QGEMM_MAX_ROWS",
+                                      _MOE_QGEMM_MAX_ROWS[qbits]))
+        if r <= max_rows:
+            _C.moe_gemm_q(out, x, w, scales, seg_off, rows, gated, qbits)
+            return out
+        w = dequantize_weight(w.flatten(0, 1), scales.flatten(0, 1), qbits,
+                              x.dtype).view(w.shape[0], w.shape[1], -1)
     if rows is not None:
-        out = torch.empty((rows.numel(), n), dtype=x.dtype, device=x.device)
         _C.moe_gemm_gather(out, x, w, seg_off, rows, gated)
-        return out
-    out = torch.empty((x.shape[0], n), dtype=x.dtype, device=x.device)
-    _C.moe_gemm(out, x, w, seg_off, gated)
+    else:
+        _C.moe_gemm(out, x, w, seg_off, gated)
     return out
 
 
