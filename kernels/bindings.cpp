@@ -117,6 +117,12 @@ void launch_sample_topk_topp(long*, int*, const T*, const float*,
                              const float*, const int*, const float*, int, int,
                              hipStream_t);
 int sample_topk_topp_max_vocab();
+void launch_token_bitmap_scatter(unsigned*, const int*, const int*, int, int,
+                                 int, int, hipStream_t);
+template <typename T>
+void launch_logits_edit(T*, const int*, const float*, const unsigned*,
+                        const int*, const unsigned*, const int*, int, int, int,
+                        int, int, int, hipStream_t);
 void launch_moe_gemm(__hip_bfloat16*, const __hip_bfloat16*,
                      const __hip_bfloat16*, const int*, const int*, int, int,
                      int, int, bool, hipStream_t);
@@ -987,6 +993,87 @@ void sample_topk_topp(torch::Tensor out, torch::Tensor logits,
   }
 }
 
+// token bitmaps: int32 [slots, W] holding the uint32 words' bits, 16-byte rows
+void check_token_bitmap(const torch::Tensor& bm, const c10::Device& dev) {
+  TORCH_CHECK(bm.scalar_type() == at::ScalarType::Int && bm.dim() == 2 &&
+              bm.is_contiguous() && bm.device() == dev &&
+              bm.size(1) % 4 == 0 && bm.size(0) < (1 << 24),
+              "token bitmap must be contiguous int32 [slots, W], W % 4 == 0");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(bm.data_ptr()) % 16 == 0);
+}
+
+void check_int_list(const torch::Tensor& t, long n, const c10::Device& dev) {
+  TORCH_CHECK(t.scalar_type() == at::ScalarType::Int && t.dim() == 1 &&
+              t.size(0) == n && t.is_contiguous() && t.device() == dev);
+}
+
+void token_bitmap_scatter(torch::Tensor bitmap, torch::Tensor slots,
+                          torch::Tensor tokens, int64_t vocab) {
+  TORCH_CHECK(bitmap.is_cuda());
+  const auto dev = bitmap.device();
+  check_token_bitmap(bitmap, dev);
+  const long P = slots.numel();
+  check_int_list(slots, P, dev);
+  check_int_list(tokens, P, dev);
+  TORCH_CHECK(vocab >= 0 && vocab <= bitmap.size(1) * 32 && P < (1L << 31),
+              "vocab exceeds the bitmap row");
+  if (P == 0 || bitmap.size(0) == 0) return;
+  launch_token_bitmap_scatter(ptr<unsigned>(bitmap), slots.data_ptr<int>(),
+                              tokens.data_ptr<int>(), (int)P,
+                              (int)bitmap.size(0), (int)bitmap.size(1),
+                              (int)vocab, current_stream());
+}
+
+void logits_edit(torch::Tensor logits, torch::Tensor rows,
+                 torch::Tensor penalties, c10::optional<torch::Tensor> seen,
+                 c10::optional<torch::Tensor> seen_slots,
+                 c10::optional<torch::Tensor> allow,
+                 c10::optional<torch::Tensor> allow_slots) {
+  TORCH_CHECK(logits.dim() == 2 && logits.is_cuda() && logits.is_contiguous());
+  const auto dev = logits.device();
+  const long N = logits.size(0);
+  const long V = logits.size(1);
+  TORCH_CHECK(V % 8 == 0 && V < (1L << 30) && N < (1L << 31),
+              "logits_edit needs V % 8 == 0");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0);
+  const long E = rows.numel();
+  check_int_list(rows, E, dev);
+  TORCH_CHECK(penalties.scalar_type() == at::ScalarType::Float &&
+              penalties.dim() == 1 && penalties.size(0) == E &&
+              penalties.is_contiguous() && penalties.device() == dev);
+  const long W = ((V + 31) / 32 + 3) / 4 * 4;
+  const unsigned* sp = nullptr;
+  const unsigned* ap = nullptr;
+  const int* ssp = nullptr;
+  const int* asp = nullptr;
+  int n_seen = 0, n_allow = 0;
+  if (seen.has_value()) {
+    TORCH_CHECK(seen_slots.has_value(), "seen needs seen_slots");
+    check_token_bitmap(*seen, dev);
+    check_int_list(*seen_slots, E, dev);
+    TORCH_CHECK(seen->size(1) == W, "seen bitmap width does not fit V");
+    sp = cptr<unsigned>(*seen);
+    ssp = seen_slots->data_ptr<int>();
+    n_seen = (int)seen->size(0);
+  }
+  if (allow.has_value()) {
+    TORCH_CHECK(allow_slots.has_value(), "allow needs allow_slots");
+    check_token_bitmap(*allow, dev);
+    check_int_list(*allow_slots, E, dev);
+    TORCH_CHECK(allow->size(1) == W, "allow bitmap width does not fit V");
+    ap = cptr<unsigned>(*allow);
+    asp = allow_slots->data_ptr<int>();
+    n_allow = (int)allow->size(0);
+  }
+  if (E == 0 || N == 0 || (n_seen == 0 && n_allow == 0)) return;
+  DISPATCH_FLOATING(logits.scalar_type(), {
+    launch_logits_edit<scalar_t>(ptr<scalar_t>(logits), rows.data_ptr<int>(),
+                                 penalties.data_ptr<float>(), sp, ssp, ap, asp,
+                                 (int)E, (int)N, (int)V, (int)W, n_seen,
+                                 n_allow, current_stream());
+  });
+}
+
 void logsoftmax_topk(torch::Tensor topv, torch::Tensor topi,
                      torch::Tensor chosen_lp, torch::Tensor ranks,
                      torch::Tensor logits, torch::Tensor chosen) {
@@ -1082,6 +1169,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused top-k / top-p sampling, radix-select cut + race (CDNA4)");
   m.def("sample_topk_topp_max_vocab", &sample_topk_topp_max_vocab,
         "largest vocab sample_topk_topp serves");
+  m.def("token_bitmap_scatter", &token_bitmap_scatter,
+        "OR (slot, token) pairs into a per-slot token bitmap");
+  m.def("logits_edit", &logits_edit,
+        "bitmap-driven repetition penalty + allow mask, in place (CDNA4)");
   m.def("lora_bgmv", &lora_bgmv,
         "batched multi-LoRA shrink+expand for mixed-adapter batches (CDNA4)");
   m.def("lora_sgmv", &lora_sgmv,

@@ -543,6 +543,27 @@ class GuidedState:
             pass
         return allowed
 
+    def allowed_bitmap(self, vocab: int):
+        """``allowed_token_ids()`` packed as a token-bitmap row (numpy uint32,
+        ops.pack_token_bitmap) for the fused sampler's logits_edit; packed
+        once per automaton state and kept next to the cached list."""
+        from ..ops import pack_token_bitmap
+
+        allowed = self.allowed_token_ids()
+        if allowed is None:
+            return None
+        if self.dead:
+            return pack_token_bitmap(allowed, vocab)
+        cache = self.automaton.__dict__.setdefault("_allowed_bitmap_cache", {})
+        key = (self.state, vocab)
+        try:
+            packed = cache.get(key)
+        except TypeError:  # unhashable state: the list is not cached either
+            return pack_token_bitmap(allowed, vocab)
+        if packed is None:
+            packed = cache[key] = pack_token_bitmap(allowed, vocab)
+        return packed
+
     def advance(self, token_id: int) -> None:
         if self.dead or token_id == self.eos_token_id:
             return

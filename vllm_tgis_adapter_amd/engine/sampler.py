@@ -10,8 +10,13 @@ Greedy and plain temperature-sampling rows take the fused HIP kernel
 (kernels/sampling.hip, exponential-race identity) in one pass; batches with
 top-k/top-p rows take its radix-select sibling
 (kernels/sampling_topk_topp.hip) when the logits are bf16/f16 on the GPU.
-Penalties, processors, guided masks, and top-k/top-p over f32 or CPU logits
-run the vectorised torch path.
+Repetition-penalty and guided rows stay on those kernels too: their token
+sets (seen in prompt + output, allowed by the automaton) are device bitmaps,
+1 bit per vocab entry, and kernels/logits_edit.hip edits the logits in place
+from them before the sampler and the deferred logprob kernel read them — no
+host sync, so the pipelined step keeps overlapping.  Logits processors, and
+penalties / guided masks / top-k/top-p over CPU logits (top-k/top-p over f32
+too), run the vectorised torch path.
 """
 
 from __future__ import annotations
@@ -31,6 +36,10 @@ import os as _os_mod
 # deferred (async) logprob extraction on the fused path; VTA_DEFER_LP=0
 # falls back to the synchronous slow-path extraction
 _DEFER_LP = _os_mod.environ.get("VTA_DEFER_LP", "1") == "1"
+
+# slots the seen-bitmap pool doubles up to before it evicts (16 KB each at
+# V = 128256); a batch with more penalised rows than this still grows it
+_SEEN_POOL_CAP = 1024
 
 
 @dataclass
@@ -67,6 +76,172 @@ class Sampler:
         self._pin: dict = {}
         self._pin_flip = 0
         self._pending_lp = None  # deferred logprob tensors (finish_fused)
+        # seen-token bitmaps of penalised requests (logits_edit): device pool
+        # int32 [slots, W]; entry = [request, all_token_ids scattered so far,
+        # last-used tick] per slot, id(request) -> slot for the lookup
+        self._seen: Optional[torch.Tensor] = None
+        self._seen_entries: list = []
+        self._seen_free: list[int] = []
+        self._seen_of: dict[int, int] = {}
+        self._seen_tick = 0
+
+    def _h2d_array(self, name: str, arr) -> torch.Tensor:
+        """_h2d_list for a numpy array: one pinned staging copy, async upload."""
+        src = torch.from_numpy(arr)
+        if self.device != "cuda":
+            return src
+        n = src.numel()
+        key = f"{name}.{self._pin_flip}"
+        buf = self._pin.get(key)
+        if buf is None or buf.numel() < n:
+            buf = torch.empty(max(n, 256), dtype=src.dtype, pin_memory=True)
+            self._pin[key] = buf
+        staging = buf[:n].view(src.shape)
+        staging.copy_(src)
+        return staging.to(self.device, non_blocking=True)
+
+    def _grow_seen_pool(self, cap: int, words: int, device) -> None:
+        old = self._seen
+        have = 0 if old is None else old.shape[0]
+        pool = torch.zeros((cap, words), dtype=torch.int32, device=device)
+        if have:
+            pool[:have].copy_(old)
+        self._seen = pool
+        self._seen_entries.extend([None] * (cap - have))
+        self._seen_free.extend(range(cap - 1, have - 1, -1))
+
+    def _alloc_seen_slot(self, in_batch: set) -> int:
+        """A free slot; at the pool's cap the least-recently-used slot whose
+        request is not in this batch; else a slot of the doubled pool."""
+        if not self._seen_free:
+            ents = self._seen_entries
+            victim = None
+            if len(ents) >= _SEEN_POOL_CAP:
+                for s, ent in enumerate(ents):
+                    if id(ent[0]) not in in_batch and (
+                            victim is None or ent[2] < ents[victim][2]):
+                        victim = s
+            if victim is not None:
+                del self._seen_of[id(ents[victim][0])]
+                ents[victim] = None
+                return victim
+            self._grow_seen_pool(2 * len(ents), self._seen.shape[1],
+                                 self._seen.device)
+        return self._seen_free.pop()
+
+    def _update_seen_pool(
+        self, logits: torch.Tensor, requests: list[Request],
+        pen_rows: list[int],
+    ) -> dict[int, int]:
+        """Bring the seen bitmap of every penalised row up to date with its
+        request's prompt + output tokens: newly assigned (or rewound) slots
+        are zeroed and all rows' new (slot, token) pairs go up in one copy and
+        one scatter launch.  Returns row -> slot.  A slot belongs to a Request
+        OBJECT (ids are reused); preemption or an abort only leaves a slot
+        stale until it is evicted."""
+        import numpy as np
+
+        from .. import ops as _ops
+
+        vocab = logits.shape[1]
+        words = _ops.token_bitmap_words(vocab)
+        if (self._seen is None or self._seen.shape[1] != words
+                or self._seen.device != logits.device):
+            self._seen = None
+            self._seen_entries, self._seen_free, self._seen_of = [], [], {}
+            cap = 64
+            while cap < len(pen_rows):
+                cap *= 2
+            self._grow_seen_pool(cap, words, logits.device)
+        self._seen_tick += 1
+        ents = self._seen_entries
+        in_batch = {id(r) for r in requests}
+        fresh: list[int] = []
+        pair_slots: list[int] = []
+        pair_toks: list[int] = []
+        slot_of_row: dict[int, int] = {}
+        for i in pen_rows:
+            req = requests[i]
+            n_prompt = len(req.prompt_token_ids)
+            n_all = n_prompt + len(req.output_token_ids)
+            slot = self._seen_of.get(id(req))
+            ent = ents[slot] if slot is not None else None
+            if ent is None or ent[0] is not req:
+                slot = self._alloc_seen_slot(in_batch)
+                ents = self._seen_entries
+                ent = ents[slot] = [req, 0, 0]
+                self._seen_of[id(req)] = slot
+                fresh.append(slot)
+            elif n_all < ent[1]:  # history shrank: rebuild from scratch
+                ent[1] = 0
+                fresh.append(slot)
+            upto = ent[1]
+            if upto >= n_prompt:  # the steady state: one new output token
+                new = req.output_token_ids[upto - n_prompt:]
+            else:
+                new = req.prompt_token_ids[upto:] + req.output_token_ids
+            pair_slots.extend([slot] * len(new))
+            pair_toks.extend(new)
+            ent[1] = n_all
+            ent[2] = self._seen_tick
+            slot_of_row[i] = slot
+        if fresh:
+            # index_fill_ on the slot axis stays asynchronous (see `ban`)
+            self._seen.index_fill_(
+                0, self._h2d_list("seen_fresh", fresh, torch.long), 0)
+        if pair_toks:
+            pairs = self._h2d_array(
+                "seen_pairs", np.array([pair_slots, pair_toks], dtype=np.int32))
+            _ops.token_bitmap_scatter(self._seen, pairs[0], pairs[1], vocab)
+        return slot_of_row
+
+    def _launch_logits_edit(
+        self, logits: torch.Tensor, requests: list[Request],
+        edit_rows: list[int],
+    ) -> None:
+        """Repetition penalty and guided masks of ``edit_rows`` applied to
+        ``logits`` in place by ops.logits_edit, without a host sync: seen
+        bitmaps from the per-sampler pool, allow bitmaps packed once per
+        automaton state and uploaded as one [G, W] copy."""
+        import numpy as np
+
+        from .. import ops as _ops
+
+        vocab = logits.shape[1]
+        pen_rows = [i for i in edit_rows
+                    if requests[i].sampling_params.repetition_penalty != 1.0]
+        seen_slot = (self._update_seen_pool(logits, requests, pen_rows)
+                     if pen_rows else {})
+        allow_rows: list = []
+        # one upload: rows, penalties (f32 bits), seen slots, allow slots
+        meta = np.empty((4, len(edit_rows)), dtype=np.int32)
+        pens = meta[1].view(np.float32)
+        for j, i in enumerate(edit_rows):
+            req = requests[i]
+            packed = None
+            gs = req.guided_state
+            if gs is not None:
+                pack = getattr(gs, "allowed_bitmap", None)
+                if pack is not None:
+                    packed = pack(vocab)
+                else:
+                    ids = gs.allowed_token_ids()
+                    if ids is not None:
+                        packed = _ops.pack_token_bitmap(ids, vocab)
+            meta[0, j] = i
+            pens[j] = req.sampling_params.repetition_penalty
+            meta[2, j] = seen_slot.get(i, -1)
+            meta[3, j] = -1 if packed is None else len(allow_rows)
+            if packed is not None:
+                allow_rows.append(packed)
+        dmeta = self._h2d_array("edit_meta", meta)
+        allow = None
+        if allow_rows:
+            allow = self._h2d_array(
+                "edit_allow", np.stack(allow_rows).view(np.int32))
+        _ops.logits_edit(
+            logits, dmeta[0], dmeta[1].view(torch.float32),
+            self._seen if pen_rows else None, dmeta[2], allow, dmeta[3])
 
     def _h2d_list(self, name: str, data: list, dtype: torch.dtype) -> torch.Tensor:
         if self.device != "cuda":
@@ -97,8 +272,12 @@ class Sampler:
         """Launch the fused one-pass sampler WITHOUT host sync.
 
         Returns the device token-id tensor (caller syncs via .tolist()) when
-        every row is greedy, plain temperature, or top-k/top-p sampling — no
-        penalties, processors or guided masks — else None.  Top-k/top-p
+        every row is greedy, plain temperature, or top-k/top-p sampling with
+        no logits processors, else None.  Repetition-penalty and guided
+        rows qualify where ops.logits_edit_usable holds (GPU logits,
+        V % 8 == 0, VTA_SAMPLE_EDIT != 0): their edits are launched here,
+        after the EOS ban and before the sampler, from device bitmaps.
+        Top-k/top-p
         rows qualify only where the fused HIP sampler serves the logits
         (bf16/f16 on the GPU); on CPU, under VTA_FORCE_REFERENCE, or with
         f32 logits such a batch returns None as before.  Rows that
@@ -116,18 +295,21 @@ class Sampler:
         any_sampling = False
         any_filter = False  # some sampling row sets top-k / top-p
         filter_ok = _ops.sample_topk_topp_usable(logits)
+        edit_ok = _ops.logits_edit_usable(logits)
         ban_rows: list[int] = []  # rows with min_tokens pending: EOS banned
         ban_eos: list[int] = []
         lp_rows: list[int] = []   # rows that want logprob details (deferred)
+        edit_rows: list[int] = []  # penalty / guided rows (logits_edit)
         for i, req in enumerate(requests):
             p = req.sampling_params
-            if (
-                p.repetition_penalty != 1.0
-                or p.logits_processors
-                or req.guided_state is not None
-            ):
+            if p.logits_processors:
                 simple = False
                 break
+            if p.repetition_penalty != 1.0 or req.guided_state is not None:
+                if not edit_ok:  # CPU / force-reference / VTA_SAMPLE_EDIT=0
+                    simple = False
+                    break
+                edit_rows.append(i)
             if p.logprobs is not None:
                 if not _DEFER_LP:  # kill switch: old behavior = slow path
                     simple = False
@@ -163,6 +345,8 @@ class Sampler:
             flat = [r * vocab + e for r, e in zip(ban_rows, ban_eos)]
             logits.view(-1).index_fill_(
                 0, self._h2d_list("ban", flat, torch.long), _NEG_INF)
+        if edit_rows:
+            self._launch_logits_edit(logits, requests, edit_rows)
         if not _ops.native_enabled(logits):
             # CPU / force-reference: plain argmax-or-race, still deferred-sync
             if not any_sampling:

@@ -493,6 +493,75 @@ def sample_topk_topp(
     _C.sample_topk_topp(out, logits, temps, noise, top_k, top_p, kept)
 
 
+def token_bitmap_words(vocab: int) -> int:
+    """uint32 words per token-bitmap row: ceil(V / 32) rounded up to a
+    multiple of 4, so rows are 16-byte aligned."""
+    return ((vocab + 31) // 32 + 3) // 4 * 4
+
+
+def pack_token_bitmap(ids, vocab: int):
+    """Host-side bitmap row (numpy uint32 [W]) with the bit of every id in
+    [0, vocab) set: bit ``t & 31`` of word ``t >> 5`` stands for token t."""
+    import numpy as np
+
+    bits = np.zeros(token_bitmap_words(vocab) * 32, dtype=np.uint8)
+    idx = np.asarray(ids, dtype=np.int64).reshape(-1)
+    bits[idx[(idx >= 0) & (idx < vocab)]] = 1
+    return np.packbits(bits, bitorder="little").view("<u4")
+
+
+def token_bitmap_scatter(
+    bitmap: torch.Tensor,  # [slots, W] int32 (the uint32 words' bits)
+    slots: torch.Tensor,   # [P] int32
+    tokens: torch.Tensor,  # [P] int32
+    vocab: int | None = None,  # tokens outside [0, vocab) are dropped
+) -> torch.Tensor:
+    """OR the bit of every (slot, token) pair into ``bitmap``, in place.
+    Duplicates, slots outside the bitmap and tokens outside the vocab are
+    harmless.  Launch only, no host sync."""
+    if vocab is None:
+        vocab = bitmap.shape[1] * 32
+    if _native(bitmap):
+        _C.token_bitmap_scatter(bitmap, slots, tokens, vocab)
+        return bitmap
+    return reference.token_bitmap_scatter(bitmap, slots, tokens, vocab)
+
+
+def logits_edit_usable(logits: torch.Tensor) -> bool:
+    """The bitmap-driven edit kernel serves contiguous 2-D bf16/f16/f32 GPU
+    logits with V % 8 == 0 (a bitmap byte is one 8-token piece).
+    ``VTA_SAMPLE_EDIT=0``, read per call, turns the route off."""
+    return (native_enabled(logits) and logits.dim() == 2
+            and logits.dtype in (torch.bfloat16, torch.float16, torch.float32)
+            and logits.is_contiguous() and logits.shape[1] % 8 == 0
+            and logits.shape[1] > 0
+            and os.environ.get("VTA_SAMPLE_EDIT", "1") != "0")
+
+
+def logits_edit(
+    logits: torch.Tensor,       # [N, V], edited in place
+    rows: torch.Tensor,         # [E] int32 logit row of each edit row
+    penalties: torch.Tensor,    # [E] float32 repetition penalty, 1.0 = none
+    seen: torch.Tensor | None,  # [S, W] int32 bitmaps of seen tokens
+    seen_slots: torch.Tensor | None,   # [E] int32 row of `seen`, -1 = none
+    allow: torch.Tensor | None,        # [G, W] int32 bitmaps of allowed tokens
+    allow_slots: torch.Tensor | None,  # [E] int32 row of `allow`, -1 = none
+) -> torch.Tensor:
+    """Repetition penalty and guided-decoding mask as one sparse in-place
+    pass (E7): a seen token's logit becomes ``x / p if x > 0 else x * p``
+    (f32, rounded once), then a token outside the allow set becomes -inf.
+    Rows not listed in ``rows`` are not touched; the bitmaps decide which
+    logits are read or written at all.  Launch only, no host sync."""
+    if _native(logits):
+        assert logits.dim() == 2 and logits.shape[1] % 8 == 0, \
+            "logits_edit needs logits_edit_usable()"
+        _C.logits_edit(logits, rows, penalties, seen, seen_slots,
+                       allow, allow_slots)
+        return logits
+    return reference.logits_edit(logits, rows, penalties, seen, seen_slots,
+                                 allow, allow_slots)
+
+
 def logsoftmax_topk_usable(logits: torch.Tensor) -> bool:
     # V >= 2048 guarantees every lane feeds both accumulator pairs
     return (native_enabled(logits) and logits.dtype == torch.bfloat16

@@ -176,3 +176,44 @@ def moe_combine(ye: torch.Tensor, pos: torch.Tensor, weights: torch.Tensor) -> t
     """out[t] = sum_j weights[t, j] * ye[pos[t, j]], f32 sum rounded once."""
     rows = ye[pos.long()].float()                    # [T, k, H]
     return (rows * weights.float()[..., None]).sum(dim=1).to(ye.dtype)
+
+
+def _bitmap_bits(words: torch.Tensor, vocab: int) -> torch.Tensor:
+    """int32 [W] bitmap row -> bool [vocab]: bit (t & 31) of word (t >> 5)."""
+    shifts = torch.arange(32, dtype=torch.int32, device=words.device)
+    return ((words.unsqueeze(1) >> shifts) & 1).bool().reshape(-1)[:vocab]
+
+
+def token_bitmap_scatter(bitmap: torch.Tensor, slots: torch.Tensor,
+                         tokens: torch.Tensor, vocab: int) -> torch.Tensor:
+    """OR the bit of every in-range (slot, token) pair into the int32
+    [slots, W] bitmap, in place."""
+    n, w = bitmap.shape
+    s, t = slots.long(), tokens.long()
+    ok = (s >= 0) & (s < n) & (t >= 0) & (t < vocab)
+    bits = torch.zeros(n, w * 32, dtype=torch.bool, device=bitmap.device)
+    bits[s[ok], t[ok]] = True
+    weights = 1 << torch.arange(32, dtype=torch.int64, device=bitmap.device)
+    words = (bits.view(n, w, 32).long() * weights).sum(-1)
+    words = (words + 2**31) % 2**32 - 2**31  # the uint32 word's bits as int32
+    bitmap |= words.to(torch.int32)
+    return bitmap
+
+
+def logits_edit(logits, rows, penalties, seen, seen_slots, allow, allow_slots):
+    """Repetition penalty (x / p if x > 0 else x * p, in f32) over each edit
+    row's seen bitmap, then -inf outside its allow bitmap; rounded once, in
+    place.  Slot -1 (or a missing bitmap) means no such edit for the row."""
+    vocab = logits.shape[1]
+    for e, row in enumerate(rows.tolist()):
+        x = logits[row].float()
+        pen = penalties[e].float()
+        ss = int(seen_slots[e]) if seen is not None else -1
+        if ss >= 0 and float(pen) != 1.0:
+            hit = _bitmap_bits(seen[ss], vocab)
+            x = torch.where(hit, torch.where(x > 0, x / pen, x * pen), x)
+        sa = int(allow_slots[e]) if allow is not None else -1
+        if sa >= 0:
+            x = x.masked_fill(~_bitmap_bits(allow[sa], vocab), float("-inf"))
+        logits[row] = x.to(logits.dtype)
+    return logits
